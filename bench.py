@@ -11,15 +11,27 @@ Synthetic data: images U[-1,1) (the mobilenet_v2
 preprocess range), captions [<start>] + U{4..V-1}^(len-2) + [<end>], len ~
 U{8..32}, zero padded; random-init weights (no checkpoints offline).
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times --steps steps and prints the JSON line
+(metric, value, ms_per_step, ...). --dump-outputs DIR then writes what the
+last timed step computed (dump_outputs below) for output-for-output
+comparison of two builds: inputs and weights are seeded, identical from run to
+run.
+
+--full (one GPU) adds these objects to the JSON line, each a run of its own
+after the timed steps:
   roofline      the dominant kernel (implicit-GEMM conv, the P3 subnet 3x3
                 shape) timed live with HIP events on its stream
   cpu_baseline  the CPU oracle (oracle/ref_cpu.py, torch fp32) training step on
                 this host's cores, rank 0 at N=1 only, bounded sample
   cpu_ref_logit_delta  max |logit_gpu(fp32 mode) - logit_cpu| on one image
+  c4_per_gpu_b64, c4_split_step_b64, fp32_mode_step, headline_r50fpn_fwd,
+  c3_fe_fwd, c5_decode, input_pipeline   the other BASELINE configurations
+(--no-cpu-baseline / --no-extra drop the CPU legs / the other configurations
+from a --full run.)
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N>1 under
-torch.distributed.run (one rank per GPU, RCCL).
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]
+[--dump-outputs DIR]; for N>1 under torch.distributed.run (one rank per GPU,
+RCCL).
 """
 import argparse
 import json
@@ -401,6 +413,26 @@ def logit_delta(model, image=224):
         fpnmt.set_precision(prev)
 
 
+DUMP_SAMPLE = 1 << 20  # parameters kept by --dump-outputs (4 MB of fp32)
+
+
+def dump_outputs(path, eng, loss):
+    """--dump-outputs: what a caller of TrainEngine.step has after the last
+    timed step, as float32 <name>.npy files:
+      loss           (1,) the loss step() returned
+      params_sample  (DUMP_SAMPLE,) the updated fp32 master weights, which
+                     step() leaves in the model: a fixed seeded sample of the
+                     parameter arena (the whole arena is ~420 MB), in arena
+                     order"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = eng.arena.flat
+    idx = np.sort(np.random.default_rng(20240229).integers(0, flat.numel(), min(DUMP_SAMPLE, flat.numel())))
+    sample = flat[torch.from_numpy(idx).to(flat.device)]
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "params_sample.npy"), sample.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -416,11 +448,16 @@ def main():
     ap.add_argument("--precision", default="bf16")
     ap.add_argument("--dropout", type=float, default=0.1)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: after the timed steps also run the roofline kernel, the CPU oracle legs and "
+                         "the other configurations (extra objects on the JSON line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle legs")
     ap.add_argument("--roofline-only", action="store_true")
     ap.add_argument("--headline-only", action="store_true", help="ResNet-50-FPN fwd batch 64 only")
     ap.add_argument("--c3-only", action="store_true", help="C3 R101-FPN FeatureExtractor 512^2 only")
-    ap.add_argument("--no-extra", action="store_true", help="skip the headline / C3 / C5 probes")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the headline / C3 / C5 probes")
     ap.add_argument("--c5-only", action="store_true", help="C5 batched beam decode only")
     ap.add_argument("--input-only", action="store_true", help="input pipeline (resize + preprocess) only")
     ap.add_argument("--backbone", default="resnet50")
@@ -514,6 +551,8 @@ def main():
     torch.cuda.synchronize()
     dt = fdist.allreduce_max_scalar(time.perf_counter() - t0)
     loss_v = float(loss.item()) if loss is not None else float("nan")
+    if args.dump_outputs and rank == 0 and loss is not None:
+        dump_outputs(args.dump_outputs, eng, loss)  # before anything else steps the model
     timeline = None
     if world > 1 and eng.split and eng.use_graph:
         # one more (untimed) replayed step with HIP events around every stage
@@ -558,7 +597,7 @@ def main():
         }
     if rank == 0 and timeline is not None:
         out["exchange_timeline_rank0"] = timeline
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         out["roofline"] = roofline_probe(args.batch)
 
         if not args.no_cpu_baseline:

@@ -43,7 +43,7 @@ json.dump(r, open(d + "/roofline_pmc.json", "w"), indent=1)
 print("traffic", r["hbm_bytes_per_launch"], "reread", r["reread_factor"])
 PY
 rc=$?; echo "== pmc json rc=$rc"; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 500 python bench.py > $D/bench.json 2> $D/bench.err; rc=$?
+timeout -k 10 500 python bench.py --full > $D/bench.json 2> $D/bench.err; rc=$?
 echo "== bench rc=$rc"; cut -c1-400 $D/bench.json; [ $rc -eq 0 ] || { tail -20 $D/bench.err; exit $rc; }
 i=0
 for grp in "SQ_VALU_MFMA_BUSY_CYCLES,SQ_BUSY_CYCLES,SQ_WAVE_CYCLES,SQ_WAIT_INST_ANY,SQ_WAIT_ANY,SQ_INSTS_MFMA,GRBM_GUI_ACTIVE" "FETCH_SIZE" "WRITE_SIZE"; do

@@ -13,7 +13,7 @@ echo "== tests rc=$rc"; grep -E "FAILED|passed|failed" $D/tests.txt | tail -8; c
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $D/smoke.txt 2>&1; rc=$?
 echo "== smoke rc=$rc"; tail -2 $D/smoke.txt; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 500 python bench.py > $D/bench.json 2> $D/bench.err; rc=$?
+timeout -k 10 500 python bench.py --full > $D/bench.json 2> $D/bench.err; rc=$?
 echo "== bench rc=$rc"; cut -c1-300 $D/bench.json; [ $rc -eq 0 ] || { tail -20 $D/bench.err; exit $rc; }
 for probe in step roof head; do
   case $probe in

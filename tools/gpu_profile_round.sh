@@ -9,7 +9,7 @@ R=${ROUND:-r02}
 D=gpurun_out/${R}f
 mkdir -p $D
 export TMPDIR=/tmp
-timeout -k 10 400 python bench.py > $D/bench.json 2> $D/bench.err; rc=$?
+timeout -k 10 400 python bench.py --full > $D/bench.json 2> $D/bench.err; rc=$?
 echo "== bench rc=$rc"; cut -c1-400 $D/bench.json; [ $rc -eq 0 ] || { tail -20 $D/bench.err; exit $rc; }
 for probe in step roof head c3; do
   case $probe in

@@ -24,7 +24,7 @@ session_a() {
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $D/prof_step.log 2>&1; rc=$?
   echo "== prof step rc=$rc"; tail -1 $D/prof_step.log | cut -c1-300; [ $rc -eq 0 ] || exit $rc
   for f in "--fuse-prep off" "--fuse-prep on" "--fuse-prep off" "--fuse-prep on"; do
-    timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra $f > $D/ab.json 2>$D/ab.err || { tail -5 $D/ab.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra $f > $D/ab.json 2>$D/ab.err || { tail -5 $D/ab.err; exit 1; }
     python -c "import json;d=json.load(open('$D/ab.json'));print('[$f]', d['ms_per_step'])"
   done
   timeout -k 10 500 python -u tools/probes/fe_bwd.py 6 10000 > $D/fe_bwd.txt 2>&1; rc=$?
@@ -63,7 +63,7 @@ session_c() {
   for r in 1 2; do
     for lib in base new; do
       if [ $lib = base ]; then cp abbase/libfpnmt_base.so $L; else cp /tmp/new.so $L; fi
-      timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
       python -c "import json;d=json.load(open('$D/ab.json'));print('[$lib]', d['ms_per_step'])"
     done
   done
@@ -90,7 +90,7 @@ session_d() {
   for r in 1 2; do
     for lib in base new; do
       if [ $lib = base ]; then cp abbase/libfpnmt_base.so $L; else cp /tmp/new.so $L; fi
-      timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
       python -c "import json;d=json.load(open('$D/ab.json'));print('[$lib]', d['ms_per_step'], d['roofline']['avg_launch_ms'])"
     done
   done
@@ -145,7 +145,7 @@ session_g() {
   for r in 1 2; do
     for lib in base new; do
       if [ $lib = base ]; then cp abbase/libfpnmt_base.so $L; else cp /tmp/new.so $L; fi
-      timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
       python -c "import json;d=json.load(open('$D/ab.json'));print('[$lib]', d['ms_per_step'], d['roofline']['avg_launch_ms'])"
     done
   done
@@ -168,7 +168,7 @@ session_h() {
   for r in 1 2; do
     for lib in base new; do
       if [ $lib = base ]; then cp abbase/libfpnmt_base.so $L; else cp /tmp/new.so $L; fi
-      timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
       python -c "import json;d=json.load(open('$D/ab.json'));print('[$lib]', d['ms_per_step'], d['roofline']['avg_launch_ms'])"
     done
   done
@@ -191,7 +191,7 @@ session_i() {
     -k "fused_optimizer_prep or checkpoint or bitwise or identity_residual or split" > $D/tests.txt 2>&1; rc=$?
   echo "== tests rc=$rc"; tail -3 $D/tests.txt; [ $rc -le 1 ] || exit $rc
   for f in "--fuse-identity off" "--fuse-identity on" "--fuse-identity off" "--fuse-identity on"; do
-    timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra $f > $D/ab.json 2>$D/ab.err || { tail -5 $D/ab.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra $f > $D/ab.json 2>$D/ab.err || { tail -5 $D/ab.err; exit 1; }
     python -c "import json;d=json.load(open('$D/ab.json'));print('[$f]', d['ms_per_step'], d['roofline']['avg_launch_ms'])"
   done
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $D/prof_step.log 2>&1; rc=$?
@@ -222,7 +222,7 @@ session_k() {
   for r in 1 2; do
     for lib in base new; do
       if [ $lib = base ]; then cp abbase/libfpnmt_base.so $L; else cp /tmp/new.so $L; fi
-      timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
       python -c "import json;d=json.load(open('$D/ab.json'));print('[$lib]', d['ms_per_step'], d['roofline']['avg_launch_ms'])"
     done
   done
@@ -250,7 +250,7 @@ session_l() {
   for r in 1 2; do
     for lib in base new; do
       if [ $lib = base ]; then cp abbase/libfpnmt_base.so $L; else cp /tmp/new.so $L; fi
-      timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
       python -c "import json;d=json.load(open('$D/ab.json'));print('[$lib]', d['ms_per_step'], d['roofline']['avg_launch_ms'])"
     done
   done
@@ -287,7 +287,7 @@ session_n() {
   mkdir -p $D
   run() {  # name, env assignments...
     local name=$1; shift
-    env "$@" timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/$name.json 2>$D/$name.err || { tail -5 $D/$name.err; exit 1; }
+    env "$@" timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/$name.json 2>$D/$name.err || { tail -5 $D/$name.err; exit 1; }
     python -c "import json;d=json.load(open('$D/$name.json'));print('[$name]', d['ms_per_step'], d['loss'])"
   }
   for r in 1 2; do
@@ -311,7 +311,7 @@ session_o() {
   echo "== tests rc=$rc"; tail -3 $D/tests.txt; [ $rc -eq 0 ] || { grep -E "Error|assert|FAILED" $D/tests.txt | head -20; exit $rc; }
   for r in 1 2; do
     for f in off on; do
-      timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra --fuse-block-act $f > $D/ab_$f.json 2>$D/ab_$f.err || { tail -5 $D/ab_$f.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra --fuse-block-act $f > $D/ab_$f.json 2>$D/ab_$f.err || { tail -5 $D/ab_$f.err; exit 1; }
       python -c "import json;d=json.load(open('$D/ab_$f.json'));print('[$f]', d['ms_per_step'], d['loss'])"
     done
   done
@@ -326,7 +326,7 @@ session_p() {
   mkdir -p $D
   run() {
     local name=$1; shift
-    env "$@" timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/$name.json 2>$D/$name.err || { tail -5 $D/$name.err; exit 1; }
+    env "$@" timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/$name.json 2>$D/$name.err || { tail -5 $D/$name.err; exit 1; }
     python -c "import json;d=json.load(open('$D/$name.json'));print('[$name]', d['ms_per_step'], repr(d['loss']))"
   }
   for r in 1 2; do
@@ -350,7 +350,7 @@ session_q() {
   echo "== tests rc=$rc"; tail -3 $D/tests.txt; [ $rc -eq 0 ] || exit $rc
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $D/smoke.txt 2>&1; rc=$?
   echo "== smoke rc=$rc"; tail -2 $D/smoke.txt; [ $rc -eq 0 ] || exit $rc
-  timeout -k 10 400 python bench.py > $D/bench.json 2> $D/bench.err; rc=$?
+  timeout -k 10 400 python bench.py --full > $D/bench.json 2> $D/bench.err; rc=$?
   echo "== bench rc=$rc"; cut -c1-300 $D/bench.json; exit $rc
 }
 
@@ -368,7 +368,7 @@ session_r() {
   for r in 1 2; do
     for lib in base new; do
       if [ $lib = base ]; then cp abbase/libfpnmt_base.so $L; else cp /tmp/new.so $L; fi
-      timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extra > $D/ab.json 2>$D/ab.err || { cp /tmp/new.so $L; tail -5 $D/ab.err; exit 1; }
       python -c "import json;d=json.load(open('$D/ab.json'));print('[$lib]', d['ms_per_step'], repr(d['loss']))"
     done
   done

@@ -50,7 +50,7 @@ session_d() {
   run $D 400 train_cond_2L.txt python -u tools/probes/train_cond.py 2L
   run $D 900 gpu_tests.txt python -u -m pytest tests -m gpu -x -q --timeout 600 --timeout-method thread
   cp gpurun_out/parity.json $D/parity.json 2>/dev/null
-  run $D 600 bench.json python bench.py
+  run $D 600 bench.json python bench.py --full
 }
 
 session_fin() {
@@ -91,7 +91,7 @@ json.dump(r, open(d + "/roofline_pmc.json", "w"), indent=1)
 print("traffic", r["hbm_bytes_per_launch"], "reread", r["reread_factor"])
 PY
   rc=$?; echo "== pmc json rc=$rc"; [ $rc -eq 0 ] || exit $rc
-  timeout -k 10 600 python bench.py > $D/bench.json 2> $D/bench.err; rc=$?
+  timeout -k 10 600 python bench.py --full > $D/bench.json 2> $D/bench.err; rc=$?
   echo "== bench rc=$rc"; cut -c1-400 $D/bench.json; [ $rc -eq 0 ] || { tail -20 $D/bench.err; exit $rc; }
 }
 
@@ -141,7 +141,7 @@ session_g() {
   run $D 300 prof_step.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra
   f=$(find $D/step -name "*kernel_trace.csv" | head -1)
   python tools/step_breakdown.py "$f" 40 > $D/step_breakdown.txt 2>&1; head -3 $D/step_breakdown.txt
-  run $D 600 bench.json python bench.py
+  run $D 600 bench.json python bench.py --full
 }
 
 session_h() {
@@ -172,7 +172,7 @@ session_j() {
   D=gpurun_out/r5${TAG:-j}; mkdir -p $D
   run $D 600 kernel_tests.txt python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_kernels.py
   run $D 900 model_tests.txt python -u -m pytest -x -v --timeout 800 --timeout-method thread tests/test_gpu_model.py -k "deferred or bitwise or early or drop or graph or greedy"
-  run $D 600 bench.json python bench.py
+  run $D 600 bench.json python bench.py --full
   run $D 300 prof_step.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra
   f=$(find $D/step -name "*kernel_trace.csv" | head -1)
   python tools/step_breakdown.py "$f" 40 > $D/step_breakdown.txt 2>&1; head -3 $D/step_breakdown.txt
@@ -185,7 +185,7 @@ session_k() {
   run $D 300 stem_tests.txt python -u -m pytest -x -v --timeout 240 --timeout-method thread tests/test_gpu_kernels.py -k stem_bwd_filter
   run $D 600 kernel_tests.txt python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_kernels.py
   run $D 900 model_tests.txt python -u -m pytest -x -v --timeout 800 --timeout-method thread tests/test_gpu_model.py -k "deferred or bitwise or graph"
-  run $D 600 bench.json python bench.py
+  run $D 600 bench.json python bench.py --full
   run $D 300 prof_step.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra
   f=$(find $D/step -name "*kernel_trace.csv" | head -1)
   python tools/step_breakdown.py "$f" 40 > $D/step_breakdown.txt 2>&1; head -3 $D/step_breakdown.txt
@@ -199,7 +199,7 @@ session_l() {
   run $D 300 prof_step.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra
   f=$(find $D/step -name "*kernel_trace.csv" | head -1)
   python tools/step_breakdown.py "$f" 40 > $D/step_breakdown.txt 2>&1; head -3 $D/step_breakdown.txt; grep stem_ $D/step_breakdown.txt
-  run $D 600 bench.json python bench.py --no-cpu-baseline --no-extra --steps 20
+  run $D 600 bench.json python bench.py --full --no-cpu-baseline --no-extra --steps 20
 }
 
 session_m() {
@@ -214,7 +214,7 @@ session_n() {
   # confirmation of the tree to be committed: kernel tests, the bench line
   D=gpurun_out/r5${TAG:-n}; mkdir -p $D
   run $D 600 kernel_tests.txt python -u -m pytest -x -q --timeout 300 --timeout-method thread tests/test_gpu_kernels.py
-  run $D 600 bench.json python bench.py
+  run $D 600 bench.json python bench.py --full
 }
 
 session_o() {
@@ -228,7 +228,7 @@ session_o() {
   run $D 300 prof_step.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra
   f=$(find $D/step -name "*kernel_trace.csv" | head -1)
   python tools/step_breakdown.py "$f" 40 > $D/step_breakdown.txt 2>&1; head -3 $D/step_breakdown.txt
-  run $D 600 bench.json python bench.py --no-cpu-baseline --no-extra --steps 20
+  run $D 600 bench.json python bench.py --full --no-cpu-baseline --no-extra --steps 20
 }
 
 session_p() {

@@ -31,7 +31,7 @@ session_a() {
   cp gpurun_out/parity.json $D/parity_dp_c4.json 2>/dev/null
   FPNMT_DIST_BACKEND=gloo run $D 600 bench_world2_gloo.json python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
       --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 2 --steps 5 --warmup 2 --timeline $D/timeline2
-  run $D 900 bench.json python bench.py
+  run $D 900 bench.json python bench.py --full
 }
 
 session_b() {
@@ -41,7 +41,7 @@ session_b() {
   run $D 300 wg_lw.txt tools/bin_r6/wg_bench_lw
   try $D 900 tests.txt python -u -m pytest tests -m gpu -q -x --timeout 600 --timeout-method thread
   cp gpurun_out/parity.json $D/parity.json 2>/dev/null
-  run $D 900 bench.json python bench.py
+  run $D 900 bench.json python bench.py --full
   run $D 300 prof_step.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra
 }
 
@@ -51,7 +51,7 @@ session_c() {
   D=gpurun_out/r6${R6TAG:-c}; mkdir -p $D
   try $D 900 tests.txt python -u -m pytest tests -m gpu -q -x --timeout 600 --timeout-method thread
   cp gpurun_out/parity.json $D/parity.json 2>/dev/null
-  run $D 900 bench.json python bench.py --no-cpu-baseline
+  run $D 900 bench.json python bench.py --full --no-cpu-baseline
   run $D 300 prof_step.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra
 }
 
@@ -102,7 +102,7 @@ json.dump(r, open(d + "/roofline_pmc.json", "w"), indent=1)
 print("traffic", r["hbm_bytes_per_launch"], "reread", r["reread_factor"])
 PY
   rc=$?; echo "== pmc json rc=$rc"; [ $rc -eq 0 ] || exit $rc
-  timeout -k 10 600 python bench.py > $D/bench.json 2> $D/bench.err; rc=$?
+  timeout -k 10 600 python bench.py --full > $D/bench.json 2> $D/bench.err; rc=$?
   echo "== bench rc=$rc"; cut -c1-400 $D/bench.json; [ $rc -eq 0 ] || { tail -20 $D/bench.err; exit $rc; }
   f=$(find $D/step -name "*kernel_trace.csv" | head -1)
   python tools/step_breakdown.py "$f" 30 > $D/step_breakdown.txt 2>&1; head -3 $D/step_breakdown.txt
@@ -131,7 +131,7 @@ session_k() {
   run $D 300 prof_c5.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/c5 -o c5 -- python3 bench.py --c5-only
   try $D 900 tests.txt python -u -m pytest tests -m gpu -q -x --timeout 600 --timeout-method thread
   cp gpurun_out/parity.json $D/parity.json 2>/dev/null
-  run $D 900 bench.json python bench.py --no-cpu-baseline
+  run $D 900 bench.json python bench.py --full --no-cpu-baseline
 }
 
 session_d() {
@@ -178,7 +178,7 @@ session_m() {
   done
   run $D 300 prof_roof.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/roof -o roof -- python3 bench.py --roofline-only
   FPNMT_WIDE_CFG=6 run $D 300 prof_roof6.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/roof6 -o roof6 -- python3 bench.py --roofline-only
-  run $D 600 bench.json python bench.py --no-cpu-baseline
+  run $D 600 bench.json python bench.py --full --no-cpu-baseline
 }
 
 session_f() {
@@ -187,7 +187,7 @@ session_f() {
   D=gpurun_out/r6${R6TAG:-f}; rm -rf $D; mkdir -p $D
   try $D 600 fold_tests.txt python -u -m pytest -q --timeout 300 --timeout-method thread tests/test_gpu_kernels.py -k "bias or grouped or wide_tiles or deferred"
   try $D 900 model_tests.txt python -u -m pytest -q --timeout 600 --timeout-method thread tests/test_gpu_model.py
-  run $D 600 bench.json python bench.py --no-cpu-baseline
+  run $D 600 bench.json python bench.py --full --no-cpu-baseline
   run $D 300 prof_step.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra
   f=$(find $D/step -name "*kernel_trace.csv" | head -1)
   python tools/step_breakdown.py "$f" 30 > $D/step_breakdown.txt 2>&1; head -20 $D/step_breakdown.txt
@@ -200,7 +200,7 @@ session_r() {
   run $D 200 roof1.json python bench.py --roofline-only
   run $D 200 roof2.json python bench.py --roofline-only
   run $D 300 prof_roof.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/roof -o roof -- python3 bench.py --roofline-only
-  run $D 600 bench.json python bench.py
+  run $D 600 bench.json python bench.py --full
   FPNMT_GEMM_LOG=$D/gemm.log run $D 300 gemm_log.txt python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extra
 }
 
@@ -210,7 +210,7 @@ session_s() {
   D=gpurun_out/r6${R6TAG:-s}; rm -rf $D; mkdir -p $D
   try $D 600 conv_tests.txt python -u -m pytest -q --timeout 300 --timeout-method thread tests/test_gpu_kernels.py -k "conv"
   try $D 900 model_tests.txt python -u -m pytest -q --timeout 600 --timeout-method thread tests/test_gpu_model.py
-  run $D 600 bench.json python bench.py --no-cpu-baseline
+  run $D 600 bench.json python bench.py --full --no-cpu-baseline
   run $D 300 prof_step.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra
   f=$(find $D/step -name "*kernel_trace.csv" | head -1)
   python tools/step_breakdown.py "$f" 40 > $D/step_breakdown.txt 2>&1; head -3 $D/step_breakdown.txt
@@ -221,7 +221,7 @@ session_t() {
   D=gpurun_out/r6${R6TAG:-t}; rm -rf $D; mkdir -p $D
   try $D 600 gemm_tests.txt python -u -m pytest -q --timeout 300 --timeout-method thread tests/test_gpu_kernels.py -k "gemm or dense or linear or attention"
   try $D 900 model_tests.txt python -u -m pytest -q --timeout 600 --timeout-method thread tests/test_gpu_model.py
-  run $D 600 bench.json python bench.py --no-cpu-baseline --no-extra
+  run $D 600 bench.json python bench.py --full --no-cpu-baseline --no-extra
   run $D 300 prof_step.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/step -o step -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra
   f=$(find $D/step -name "*kernel_trace.csv" | head -1)
   python tools/step_breakdown.py "$f" 40 > $D/step_breakdown.txt 2>&1; head -3 $D/step_breakdown.txt
@@ -232,7 +232,7 @@ session_last() {
   D=gpurun_out/r6${R6TAG:-last}; rm -rf $D; mkdir -p $D
   run $D 1300 tests.txt python -u -m pytest tests -m gpu -q --timeout 900 --timeout-method thread
   run $D 300 smoke.txt python -c "import __graft_entry__ as g; g.smoke()"
-  run $D 900 bench.json python bench.py
+  run $D 900 bench.json python bench.py --full
 }
 
 session_u() {
@@ -246,7 +246,7 @@ session_u() {
   FPNMT_WIDE_CFG=6 run $D 300 c3_c6.json python bench.py --c3-only
   run $D 300 c3_auto.json python bench.py --c3-only
   run $D 300 prof_head.log rocprofv3 --kernel-trace --stats --output-format csv -d $D/head -o head -- python3 bench.py --headline-only
-  run $D 600 bench.json python bench.py --no-cpu-baseline --no-extra
+  run $D 600 bench.json python bench.py --full --no-cpu-baseline --no-extra
 }
 
 "session_$1"
