@@ -15,6 +15,9 @@
 //    (value desc, then lower flat index), the new histories / cache tables of
 //    the image's beams, the best beam (argmax of the new probabilities, first
 //    max) and the result capture / stop flag (`beam_result[-1] == end`).
+//  * beam_step_log_kernel / beam_finalize_kernel: the same step as a real
+//    beam search (sums of log-probabilities, finished beams, beams that start
+//    apart) and the ranking of its n-best list; not in the reference.
 #include "common.h"
 #include <initializer_list>
 
@@ -439,6 +442,272 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(
       result_len[img] = n;
       if (ended) status[img] = 1;
     }
+  }
+}
+
+// ---- log-domain beam step (BeamDecoder mode="beam") ------------------------
+// The sibling of beam_step_kernel with a real beam-search rule: the same
+// block / wave / load shapes and the same selection rounds (kept as a copy so
+// the reference-faithful kernel above stays instruction for instruction what
+// it was), but
+//  * beams carry a sum of log-probabilities; a live beam's candidates are
+//    logit[j] + (score - max - log sum), so the second pass only adds;
+//  * a finished beam (it took <end>) offers one candidate, itself, at
+//    b*V + end_token with its score unchanged, and its logits are not read;
+//  * a beam at -inf offers nothing (step 0 starts with beam 0 alone at 0, so
+//    the beams differ from the first token on);
+//  * an image whose beams have all finished (status 1) is frozen: its rows
+//    are carried to the out tables as they are and nothing else is touched.
+// A selection slot that found no candidate at all (every offer NaN) becomes a
+// finished beam at -inf that carries its own row: no table index is ever
+// formed from the list's sentinel.
+__global__ __launch_bounds__(BS_THREADS) void beam_step_log_kernel(
+    int beam_n, int vocab, const float* __restrict__ logits, long long ldl, float* __restrict__ beam_score,
+    int32_t* __restrict__ beam_len, int32_t* __restrict__ beam_fin, const int32_t* __restrict__ hist_in,
+    int32_t* __restrict__ hist_out, int hist_ld, int t, const int32_t* __restrict__ src_in,
+    int32_t* __restrict__ src_out, int src_ld, int end_token, int32_t* __restrict__ tok_out,
+    int32_t* __restrict__ status) {
+  const int img = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int NW = BS_THREADS / 64;
+  constexpr int NONE = 0x7fffffff;
+  __shared__ float coff[BEAM_MAX], bscore[BEAM_MAX];
+  __shared__ int blen[BEAM_MAX], bfin[BEAM_MAX], live[BEAM_MAX];
+  __shared__ float lv[BS_THREADS][BEAM_MAX];
+  __shared__ int li[BS_THREADS][BEAM_MAX];
+  __shared__ float sel_v[BEAM_MAX];
+  __shared__ int sel_i[BEAM_MAX];
+  __shared__ float red_v[NW];
+  __shared__ int red_i[NW], red_t[NW];
+  const int row0 = img * beam_n;
+  const int K = beam_n;
+  if (status[img] != 0) {  // block-uniform: frozen image
+    for (int e = tid; e < K * (t + 2); e += BS_THREADS) {
+      const int k = e / (t + 2), pos = e - k * (t + 2);
+      const int r = row0 + k;
+      hist_out[(long long)r * hist_ld + pos] = pos <= t ? hist_in[(long long)r * hist_ld + pos] : end_token;
+      if (pos <= t) src_out[(long long)r * src_ld + pos] = src_in[(long long)r * src_ld + pos];
+      else if (pos < src_ld) src_out[(long long)r * src_ld + pos] = r;
+    }
+    return;
+  }
+  if (tid < K) {
+    const float s = beam_score[row0 + tid];
+    const int f = beam_fin[row0 + tid] != 0;
+    bscore[tid] = s;
+    blen[tid] = beam_len[row0 + tid];
+    bfin[tid] = f;
+    live[tid] = !f && s > -INFINITY;  // false for NaN too
+  }
+  __syncthreads();
+  const bool vec = (vocab & 3) == 0 && (ldl & 3) == 0 && ((uintptr_t)logits & 15) == 0;
+  const int nv4 = vocab >> 2;
+  // 1. per live beam: score - logsumexp(logits row) (wave per beam row)
+  for (int b = wave; b < beam_n; b += NW) {
+    if (!live[b]) continue;  // wave-uniform
+    const float* lr = logits + (long long)(row0 + b) * ldl;
+    float mx = -INFINITY;
+    if (vec) {
+      const f32x4* l4 = (const f32x4*)lr;
+      int j = lane;
+      for (; j + 192 < nv4; j += 256) {
+        const f32x4 a = l4[j], c = l4[j + 64], d = l4[j + 128], e = l4[j + 192];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mx = fmaxf(mx, fmaxf(fmaxf(a[q], c[q]), fmaxf(d[q], e[q])));
+      }
+      for (; j < nv4; j += 64) {
+        const f32x4 a = l4[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mx = fmaxf(mx, a[q]);
+      }
+    } else {
+      for (int j = lane; j < vocab; j += 64) mx = fmaxf(mx, lr[j]);
+    }
+    mx = wave_max(mx);
+    float s = 0.f;
+    if (vec) {
+      const f32x4* l4 = (const f32x4*)lr;
+      int j = lane;
+      for (; j + 192 < nv4; j += 256) {
+        const f32x4 a = l4[j], c = l4[j + 64], d = l4[j + 128], e = l4[j + 192];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += expf(a[q] - mx);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += expf(c[q] - mx);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += expf(d[q] - mx);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += expf(e[q] - mx);
+      }
+      for (; j < nv4; j += 64) {
+        const f32x4 a = l4[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += expf(a[q] - mx);
+      }
+    } else {
+      for (int j = lane; j < vocab; j += 64) s += expf(lr[j] - mx);
+    }
+    s = wave_sum(s);
+    if (lane == 0) coff[b] = bscore[b] - (mx + logf(s));
+  }
+  __syncthreads();
+  // 2. per-thread sorted top-k of its candidates (flat index f = b * V + j)
+  float tv[BEAM_MAX];
+  int ti[BEAM_MAX];
+#pragma unroll
+  for (int k = 0; k < BEAM_MAX; ++k) {
+    tv[k] = -INFINITY;
+    ti[k] = NONE;
+  }
+  auto offer = [&](float c, int f) {
+    if (better(c, f, tv[BEAM_MAX - 1], ti[BEAM_MAX - 1])) {
+      // compile-time indices only, as in beam_step_kernel
+      float cv = c;
+      int ci = f;
+#pragma unroll
+      for (int k = 0; k < BEAM_MAX; ++k) {
+        if (better(cv, ci, tv[k], ti[k])) {
+          const float sv = tv[k];
+          const int si = ti[k];
+          tv[k] = cv;
+          ti[k] = ci;
+          cv = sv;
+          ci = si;
+        }
+      }
+    }
+  };
+  if (vec) {
+    for (int b = wave; b < beam_n; b += NW) {
+      if (!live[b]) continue;
+      const f32x4* l4 = (const f32x4*)(logits + (long long)(row0 + b) * ldl);
+      const float co = coff[b];
+      const int f0 = b * vocab;
+      int j = lane;
+      for (; j + 64 < nv4; j += 128) {
+        const f32x4 a = l4[j], c = l4[j + 64];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) offer(a[q] + co, f0 + 4 * j + q);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) offer(c[q] + co, f0 + 4 * (j + 64) + q);
+      }
+      for (; j < nv4; j += 64) {
+        const f32x4 a = l4[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) offer(a[q] + co, f0 + 4 * j + q);
+      }
+    }
+  } else {
+    const int total = beam_n * vocab;
+    for (int f = tid; f < total; f += BS_THREADS) {
+      const int b = f / vocab, j = f - b * vocab;
+      if (live[b]) offer(logits[(long long)(row0 + b) * ldl + j] + coff[b], f);
+    }
+  }
+  // a finished beam's single candidate: itself, ending in <end>
+  if (tid < K && bfin[tid]) offer(bscore[tid], tid * vocab + end_token);
+#pragma unroll
+  for (int k = 0; k < BEAM_MAX; ++k) {
+    lv[tid][k] = tv[k];
+    li[tid][k] = ti[k];
+  }
+  __syncthreads();
+  // 3. k rounds of a block arg-best over the list heads
+  int head = 0;
+  for (int round = 0; round < K; ++round) {
+    float bv = head < K ? lv[tid][head] : -INFINITY;
+    int bi = head < K ? li[tid][head] : NONE;
+    int bt = tid;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      const int ot = __shfl_xor(bt, o, 64);
+      if (better(ov, oi, bv, bi)) {
+        bv = ov;
+        bi = oi;
+        bt = ot;
+      }
+    }
+    if (lane == 0) {
+      red_v[wave] = bv;
+      red_i[wave] = bi;
+      red_t[wave] = bt;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      float wv = red_v[0];
+      int wi = red_i[0], wt = red_t[0];
+      for (int w = 1; w < NW; ++w)
+        if (better(red_v[w], red_i[w], wv, wi)) {
+          wv = red_v[w];
+          wi = red_i[w];
+          wt = red_t[w];
+        }
+      sel_v[round] = wv;
+      sel_i[round] = wi;
+      red_t[0] = wt;
+    }
+    __syncthreads();
+    if (tid == red_t[0]) ++head;
+    __syncthreads();
+  }
+  // 4. new beams: parent = flat / V, token = flat % V; an empty slot carries
+  //    its own row as a finished beam at -inf
+  for (int e = tid; e < K * (t + 2); e += BS_THREADS) {
+    const int k = e / (t + 2), pos = e - k * (t + 2);
+    const bool none = sel_i[k] == NONE;
+    const int parent = none ? k : sel_i[k] / vocab, tok = none ? end_token : sel_i[k] - parent * vocab;
+    const int r = row0 + k, pr = row0 + parent;
+    hist_out[(long long)r * hist_ld + pos] = pos <= t ? hist_in[(long long)pr * hist_ld + pos] : tok;
+    if (pos <= t) src_out[(long long)r * src_ld + pos] = src_in[(long long)pr * src_ld + pos];
+    else if (pos < src_ld) src_out[(long long)r * src_ld + pos] = r;  // next step writes its K/V at row r
+  }
+  int fin = 1;
+  if (tid < K) {
+    const bool none = sel_i[tid] == NONE;
+    const int parent = none ? tid : sel_i[tid] / vocab, tok = none ? end_token : sel_i[tid] - parent * vocab;
+    const bool pfin = none || bfin[parent];
+    fin = pfin || tok == end_token;
+    tok_out[row0 + tid] = tok;
+    beam_score[row0 + tid] = none ? -INFINITY : sel_v[tid];
+    beam_len[row0 + tid] = pfin ? blen[parent] : t + 1;
+    beam_fin[row0 + tid] = fin;
+  }
+  // 5. the image stops once every beam has finished
+  if (__syncthreads_and(fin) && tid == 0) status[img] = 1;
+}
+
+// Ranks an image's beams by score / max(len, 1)^alpha (descending, ties to
+// the lower beam index) and writes the n-best list: tokens after <start>
+// without a final <end>, zero-padded to tok_ld.
+__global__ __launch_bounds__(256) void beam_finalize_kernel(
+    int beam_n, const int32_t* __restrict__ hist, int hist_ld, const float* __restrict__ beam_score,
+    const int32_t* __restrict__ beam_len, const int32_t* __restrict__ beam_fin, float alpha,
+    int32_t* __restrict__ nbest_tok, int tok_ld, int32_t* __restrict__ nbest_len, float* __restrict__ nbest_score) {
+  const int img = blockIdx.x, tid = threadIdx.x;
+  const int row0 = img * beam_n;
+  __shared__ float key[BEAM_MAX];
+  __shared__ int rank_of[BEAM_MAX], ntok[BEAM_MAX];
+  if (tid < beam_n) {
+    const int len = beam_len[row0 + tid];
+    const float s = beam_score[row0 + tid];
+    key[tid] = alpha == 0.f ? s : s / powf((float)max(len, 1), alpha);
+    ntok[tid] = max(0, min(min(len - (beam_fin[row0 + tid] ? 1 : 0), tok_ld), hist_ld - 1));
+  }
+  __syncthreads();
+  if (tid < beam_n) {
+    int rk = 0;
+    for (int j = 0; j < beam_n; ++j) rk += better(key[j], j, key[tid], tid);
+    rank_of[tid] = rk;
+    nbest_len[row0 + rk] = ntok[tid];
+    nbest_score[row0 + rk] = key[tid];
+  }
+  __syncthreads();
+  for (int e = tid; e < beam_n * tok_ld; e += 256) {
+    const int k = e / tok_ld, pos = e - k * tok_ld;
+    nbest_tok[(long long)(row0 + rank_of[k]) * tok_ld + pos] =
+        pos < ntok[k] ? hist[(long long)(row0 + k) * hist_ld + pos + 1] : 0;
   }
 }
 
@@ -1184,6 +1453,40 @@ int fpnmt_beam_step(int n_images, int beam_n, int vocab, const float* logits, lo
                      beam_prob, hist_in, hist_out, hist_ld, t, src_in, src_out, src_ld, end_token, tok_out, result,
                      result_ld, result_len, status);
   return check_launch("beam_step");
+}
+
+int fpnmt_beam_step_log(int n_images, int beam_n, int vocab, const float* logits, long long ldl, float* beam_score,
+                        int32_t* beam_len, int32_t* beam_fin, const int32_t* hist_in, int32_t* hist_out,
+                        int hist_ld, int t, const int32_t* src_in, int32_t* src_out, int src_ld, int end_token,
+                        int32_t* tok_out, int32_t* status, fpnmt_stream_t stream) {
+  if (n_images <= 0) return 0;
+  if (beam_n <= 0 || beam_n > BEAM_MAX) return fail(FPNMT_E_UNSUPPORTED, "beam_step_log: 1 <= beam_n <= 16");
+  if (vocab < beam_n) return fail(FPNMT_E_ARG, "beam_step_log: vocab < beam_n");
+  if ((long long)beam_n * vocab > 0x7ffffffeLL || ldl < vocab)
+    return fail(FPNMT_E_ARG, "beam_step_log: beam_n * vocab exceeds int32, or ldl < vocab");
+  if (end_token < 0 || end_token >= vocab) return fail(FPNMT_E_ARG, "beam_step_log: end_token outside the vocabulary");
+  if (t < 0 || t + 2 > hist_ld || t + 1 > src_ld)
+    return fail(FPNMT_E_ARG, "beam_step_log: bad position / table widths");
+  if (!logits || !beam_score || !beam_len || !beam_fin || !hist_in || !hist_out || !src_in || !src_out || !tok_out ||
+      !status)
+    return fail(FPNMT_E_ARG, "beam_step_log: null pointer");
+  hipLaunchKernelGGL(beam_step_log_kernel, dim3(n_images), dim3(BS_THREADS), 0, S(stream), beam_n, vocab, logits, ldl,
+                     beam_score, beam_len, beam_fin, hist_in, hist_out, hist_ld, t, src_in, src_out, src_ld,
+                     end_token, tok_out, status);
+  return check_launch("beam_step_log");
+}
+
+int fpnmt_beam_finalize(int n_images, int beam_n, const int32_t* hist, int hist_ld, const float* beam_score,
+                        const int32_t* beam_len, const int32_t* beam_fin, float alpha, int32_t* nbest_tok,
+                        int tok_ld, int32_t* nbest_len, float* nbest_score, fpnmt_stream_t stream) {
+  if (n_images <= 0) return 0;
+  if (beam_n <= 0 || beam_n > BEAM_MAX) return fail(FPNMT_E_UNSUPPORTED, "beam_finalize: 1 <= beam_n <= 16");
+  if (hist_ld < 1 || tok_ld < 1) return fail(FPNMT_E_ARG, "beam_finalize: bad table widths");
+  if (!hist || !beam_score || !beam_len || !beam_fin || !nbest_tok || !nbest_len || !nbest_score)
+    return fail(FPNMT_E_ARG, "beam_finalize: null pointer");
+  hipLaunchKernelGGL(beam_finalize_kernel, dim3(n_images), dim3(256), 0, S(stream), beam_n, hist, hist_ld, beam_score,
+                     beam_len, beam_fin, alpha, nbest_tok, tok_ld, nbest_len, nbest_score);
+  return check_launch("beam_finalize");
 }
 
 }  // extern "C"

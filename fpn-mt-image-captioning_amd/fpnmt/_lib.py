@@ -207,6 +207,8 @@ SIGNATURES = {
     "fpnmt_amsgrad_step_part": [C.POINTER(AdamDesc), I, I, I, I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "fpnmt_decode_attention": [I, I, I, I, I, F, P, LL, P, LL, LL, LL, LL, P, I, I, P, LL, P],
     "fpnmt_beam_step": [I, I, I, P, LL, P, P, P, I, I, P, P, I, I, P, P, I, P, P, P],
+    "fpnmt_beam_step_log": [I, I, I, P, LL, P, P, P, P, P, I, I, P, P, I, I, P, P, P],
+    "fpnmt_beam_finalize": [I, I, P, I, P, P, P, F, P, I, P, P, P],
     "fpnmt_bn_stats": [I, LL, I, P, P, P, P, P, F, P],
     "fpnmt_bn_apply": [I, LL, I, P, P, P, P, P, F, I, P, P, P],
     "fpnmt_bn_bwd": [I, LL, I, P, P, P, P, F, I, P, P, P, P, P, P],

@@ -19,6 +19,19 @@ rows holding its history's keys/values (fpnmt_decode_attention `src`).
 
 Not reproduced on this path: the attention-weight dict of the last step (the
 reference returns it for plotting only).
+
+Those beams never part: they start identical, so top_k picks the same best
+token once per beam and the procedure is a greedy decode run beam_n times.
+`mode="beam"` keeps the cache, the tables and the graphs and changes the
+rule of the step (fpnmt_beam_step_log) and how the result is chosen
+(fpnmt_beam_finalize):
+  * beams carry a sum of log-probabilities; step 0 starts with beam 0 at 0
+    and the others at -inf, so the beams differ from the first token on;
+  * a beam that took <end> is finished: it competes with its score as it is
+    and is no longer extended; an image stops when all its beams have
+    finished (its rows are then frozen while other images decode on);
+  * the n-best list ranks the beams by score / len^length_alpha (len counts
+    the final <end>; alpha 0: the raw sum), ties to the lower beam.
 """
 from __future__ import annotations
 
@@ -41,9 +54,15 @@ def _gemm(m, n, k, dt, a, lda, b, c, ldc, bias, s):
 
 
 class BeamDecoder:
-    """decode(images) -> list of token-id lists, one per image."""
+    """decode(images) -> list of token-id lists, one per image; in
+    mode="beam", decode(images, n_best=k) -> per image the k best
+    (token ids, score) pairs, best first."""
 
-    def __init__(self, transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph=True):
+    def __init__(self, transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph=True,
+                 mode="reference", length_alpha=0.0):
+        if mode not in ("reference", "beam"):
+            raise ValueError(f"mode must be 'reference' or 'beam', got {mode!r}")
+        self.mode, self.length_alpha = mode, float(length_alpha)
         self.tr = transformer
         dec = transformer.decoder
         self.n_images, self.beam_n, self.T = n_images, beam_n, max_seq_len
@@ -72,11 +91,25 @@ class BeamDecoder:
         self.result = torch.zeros((self.n_images, T), dtype=torch.int32, device=dev)
         self.result_len = torch.zeros(self.n_images, dtype=torch.int32, device=dev)
         self.status = torch.zeros(self.n_images, dtype=torch.int32, device=dev)
+        if self.mode == "beam":
+            n, K = self.n_images, self.beam_n
+            self.score = torch.empty(R, dtype=torch.float32, device=dev)
+            self.blen = torch.zeros(R, dtype=torch.int32, device=dev)
+            self.fin = torch.zeros(R, dtype=torch.int32, device=dev)
+            self.nbest_tok = torch.zeros((n, K, T), dtype=torch.int32, device=dev)
+            self.nbest_len = torch.zeros((n, K), dtype=torch.int32, device=dev)
+            self.nbest_score = torch.zeros((n, K), dtype=torch.float32, device=dev)
 
     def _reset(self):
         R = self.R
         self.tok.fill_(self.start_token)
-        self.prob.fill_(1.0)
+        if self.mode == "beam":
+            self.score.fill_(float("-inf"))
+            self.score.view(self.n_images, self.beam_n)[:, 0] = 0.0
+            self.blen.zero_()
+            self.fin.zero_()
+        else:
+            self.prob.fill_(1.0)
         self.hist[0][:, 0] = self.start_token
         self.src[0][:, 0] = torch.arange(R, dtype=torch.int32, device=self.tok.device)
         self.result_len.zero_()
@@ -163,16 +196,26 @@ class BeamDecoder:
             out2 = lay.layernorm2(lay.mha2.dense(a2), residual=out1)
             x = lay.layernorm3(lay.ffn2(lay.ffn1(out2)), residual=out2)
         logits = tr.final_layer(x)  # (R, V) fp32
+        if self.mode == "beam":
+            call("fpnmt_beam_step_log", self.n_images, self.beam_n, self.V, ptr(logits), self.V, ptr(self.score),
+                 ptr(self.blen), ptr(self.fin), ptr(hin), ptr(hout), T + 1, t, ptr(sin), ptr(sout), T,
+                 self.end_token, ptr(self.tok), ptr(self.status), s)
+            return
         call("fpnmt_beam_step", self.n_images, self.beam_n, self.V, ptr(logits), self.V, ptr(self.prob), ptr(hin),
              ptr(hout), T + 1, t, ptr(sin), ptr(sout), T, self.end_token, ptr(self.tok), ptr(self.result), T,
              ptr(self.result_len), ptr(self.status), s)
 
     # -------------------------------------------------------------- decode
     @torch.no_grad()
-    def decode(self, images, check_every=8):
-        """images (n_images, H, W, 3) on the GPU -> list of token-id lists."""
+    def decode(self, images, check_every=8, n_best=1):
+        """images (n_images, H, W, 3) on the GPU -> list of token-id lists;
+        n_best > 1 (mode="beam"): per image a list of the n_best
+        (token-id list, score) pairs, best first."""
         if images.shape[0] != self.n_images:
             raise ValueError(f"expected {self.n_images} images, got {images.shape[0]}")
+        if n_best < 1 or n_best > (self.beam_n if self.mode == "beam" else 1):
+            raise ValueError(f"n_best {n_best}: mode {self.mode!r} with {self.beam_n} beams gives 1.."
+                             f"{self.beam_n if self.mode == 'beam' else 1}")
         dt = compute_dtype()
         if self.dt != dt:
             self.dt = dt
@@ -184,16 +227,32 @@ class BeamDecoder:
         self._reset()
         if self.use_graph and self.graphs is None:
             self._capture()
+        steps = 0
         for t in range(self.T):
             if self.graphs is not None:
                 self.graphs[t].replay()
             else:
                 self._step(t)
+            steps = t + 1
             if check_every and (t + 1) % check_every == 0 and t + 1 < self.T and bool(self.status.all()):
                 break
+        if self.mode == "beam":
+            return self._nbest(steps, n_best)
         lens = self.result_len.tolist()
         res = self.result.cpu()
         return [res[i, :lens[i]].tolist() for i in range(self.n_images)]
+
+    def _nbest(self, steps, n_best):
+        """Rank the beams of every image (fpnmt_beam_finalize over the tables
+        the last step wrote) and read the n-best list back."""
+        n, K, T = self.n_images, self.beam_n, self.T
+        call("fpnmt_beam_finalize", n, K, ptr(self.hist[steps % 2]), T + 1, ptr(self.score), ptr(self.blen),
+             ptr(self.fin), self.length_alpha, ptr(self.nbest_tok), T, ptr(self.nbest_len), ptr(self.nbest_score),
+             stream_ptr())
+        tok, lens, score = self.nbest_tok.cpu(), self.nbest_len.tolist(), self.nbest_score.tolist()
+        if n_best == 1:
+            return [tok[i, 0, :lens[i][0]].tolist() for i in range(n)]
+        return [[(tok[i, k, :lens[i][k]].tolist(), score[i][k]) for k in range(n_best)] for i in range(n)]
 
     def _capture(self):
         """One graph per position t (the step's shapes depend on t). The

@@ -137,20 +137,27 @@ class Pipeline:
         return out, attention_weights
 
     @torch.no_grad()
-    def predict_batch(self, images, max_seq_len=None, beam_n=BEAM_SEARCH_N, use_graph=True):
+    def predict_batch(self, images, max_seq_len=None, beam_n=BEAM_SEARCH_N, use_graph=True, mode="reference",
+                      length_alpha=0.0, n_best=1):
         """predict() for a batch of images (n, h, w, 3) at once: the same
         beam procedure per image (pipeline.py:82-154), with a K/V cache and a
         hipGraph per decode step (fpnmt.decode.BeamDecoder). Returns one
-        token-id list per image."""
+        token-id list per image.
+
+        mode="beam" (not in the reference, whose beams never part) runs a
+        beam search proper on the same machinery: beams scored by their sum
+        of log-probabilities, finished beams kept, the result ranked by
+        score / len^length_alpha. n_best > 1 then returns, per image, the
+        n_best (token-id list, score) pairs, best first."""
         from fpnmt.decode import BeamDecoder
         T = max_seq_len or self.max_seq_len
-        key = (images.shape[0], beam_n, T, use_graph)
+        key = (images.shape[0], beam_n, T, use_graph, mode, float(length_alpha))
         dec = getattr(self, "_decoders", {}).get(key)
         if dec is None:
             dec = BeamDecoder(self.transformer, images.shape[0], beam_n, T, self.start_token, self.end_token,
-                              use_graph=use_graph)
+                              use_graph=use_graph, mode=mode, length_alpha=length_alpha)
             self.__dict__.setdefault("_decoders", {})[key] = dec
-        return dec.decode(images)
+        return dec.decode(images, n_best=n_best)
 
 
     def evaluate(self, generator, max_seq_len):

@@ -20,6 +20,7 @@
  *   fpnmt_dropout          Dropout(rate)                models/transformer.py:173-174,219-222,262,319
  *   fpnmt_decode_attention scaled_dot_product_attention, last query row   utils/pipeline.py:105-113
  *   fpnmt_beam_step        softmax + top_k + gather + argmax of predict   utils/pipeline.py:115-147
+ *   fpnmt_beam_step_log, fpnmt_beam_finalize   beam search proper (log-prob beams, n-best)   not in the reference
  *
  * Conventions (all functions):
  *   - Return 0 on success or a negative FPNMT_E* code; never throw across the ABI.
@@ -650,6 +651,37 @@ int fpnmt_beam_step(int n_images, int beam_n, int vocab, const float* logits, lo
                     const int32_t* hist_in, int32_t* hist_out, int hist_ld, int t, const int32_t* src_in,
                     int32_t* src_out, int src_ld, int end_token, int32_t* tok_out, int32_t* result, int result_ld,
                     int32_t* result_len, int32_t* status, fpnmt_stream_t stream);
+/* Beam search proper (not in the reference, whose beams start identical and
+ * stay so). State per row: beam_score (fp32 sum of log-probabilities),
+ * beam_len (tokens after <start>, a final <end> counted), beam_fin (0 / 1);
+ * hist / src / tok_out / t as in fpnmt_beam_step. The caller starts step 0
+ * with score 0 on each image's first beam and -inf on the others.
+ * fpnmt_beam_step_log: candidates over beam_n x vocab at flat = b*vocab + j:
+ *   live beam b:     beam_score[b] + log_softmax(logits row b)[j];
+ *   finished beam b: one candidate, beam_score[b] at j = end_token;
+ *   beam at -inf:    none.
+ * Top beam_n in the order of fpnmt_beam_step (value desc, lower flat index
+ * first), parent = flat / vocab, token = flat % vocab; hist_out / src_out /
+ * tok_out as there (src_out[r][t+1] = r); beam_score[r] = candidate value; the
+ * child of a finished parent keeps beam_fin = 1 and its beam_len, a live
+ * child gets beam_len = t + 1, beam_fin = (token == end_token).
+ * status[img] = 1 once all beam_n beams have finished; an image entered with
+ * status 1 is frozen: its rows are carried to hist_out / src_out unchanged
+ * (position t+1: end_token / r) and nothing else of it is read or written.
+ * Requires beam_n <= 16, vocab >= beam_n, 0 <= end_token < vocab,
+ * hist_ld >= t + 2, src_ld >= t + 1.
+ * fpnmt_beam_finalize: per image the beams ranked by
+ * beam_score / max(beam_len, 1)^alpha (desc, ties to the lower beam; alpha 0:
+ * the raw sum) -> nbest_tok (n_images, beam_n, tok_ld) tokens after <start>
+ * without a final <end>, zero-padded; nbest_len, nbest_score (the ranking
+ * value) (n_images, beam_n), best first.                                    */
+int fpnmt_beam_step_log(int n_images, int beam_n, int vocab, const float* logits, long long ldl, float* beam_score,
+                        int32_t* beam_len, int32_t* beam_fin, const int32_t* hist_in, int32_t* hist_out,
+                        int hist_ld, int t, const int32_t* src_in, int32_t* src_out, int src_ld, int end_token,
+                        int32_t* tok_out, int32_t* status, fpnmt_stream_t stream);
+int fpnmt_beam_finalize(int n_images, int beam_n, const int32_t* hist, int hist_ld, const float* beam_score,
+                        const int32_t* beam_len, const int32_t* beam_fin, float alpha, int32_t* nbest_tok,
+                        int tok_ld, int32_t* nbest_len, float* nbest_score, fpnmt_stream_t stream);
 
 /* ---- MobileNetV2 backbone (models/mobilenet.py:43-72 ->
  * keras MobileNetV2(alpha=1.0), models/retinanet.py:274) -------------------
