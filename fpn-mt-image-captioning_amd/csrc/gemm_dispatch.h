@@ -191,12 +191,19 @@ static FILE* gemm_log() {
   return f;
 }
 
+// Fields appended after cfg= (tools/gemm_shapes.py reads key=value pairs):
+// psplit= the split count of an LDS-DMA pipe launch (cfg 130+ / 160+ / 170+),
+// tm= tn= the tile grid of a pipelined weight-gradient launch (cfg 110, logged
+// after the launch, when split= is its split count too)
 template <typename T>
-static void log_gemm(const GemmParams& p, int batch, int amode, int bmode, int cfg) {
+static void log_gemm(const GemmParams& p, int batch, int amode, int bmode, int cfg, int psplit = 0) {
   if (FILE* f = gemm_log()) {
-    std::fprintf(f, "%s a=%d b=%d c=%d M=%d N=%d K=%d batch=%d acc=%d split=%d cfg=%d\n",
+    std::fprintf(f, "%s a=%d b=%d c=%d M=%d N=%d K=%d batch=%d acc=%d split=%d cfg=%d",
                  std::is_same<T, float>::value ? "f32" : "bf16", amode, bmode, p.c_mode, p.M, p.N, p.K, batch,
                  p.accumulate, p.split_k, cfg);
+    if (psplit > 0) std::fprintf(f, " psplit=%d", psplit);
+    if (cfg == 110) std::fprintf(f, " tm=%d tn=%d", p.tiles_m, p.tiles_n);
+    std::fputc('\n', f);
     std::fflush(f);
   }
 }
@@ -504,6 +511,17 @@ static int pipe_split_for(const GemmParams& p, int batch) {
   S = std::min(S, 8);
   while (S > 1 && (long long)S * p.M * p.N > g_split_ws.part_floats) --S;
   return S < 2 ? 1 : S;
+}
+
+// the split count launch_pipe_auto runs p with (the log's psplit= field):
+// pipe_split_for's choice after launch_pipe_split's no-empty-split rounding
+static int pipe_split_logged(const GemmParams& p, int batch) {
+  int S = pipe_split_for(p, batch);
+  if (S <= 1) return 1;
+  const int nkt = p.K / 64;
+  while (S > 1 && (long long)S * p.M * p.N > g_split_ws.part_floats) --S;
+  if (S > nkt) S = nkt;
+  return cdiv(nkt, cdiv(nkt, std::max(S, 1)));
 }
 
 template <int AM>
@@ -874,7 +892,7 @@ static int scatter_via_pipe(const GemmParams& p, int batch, int amode, int bmode
   q.H = q.Ho = p.M; q.W = q.Wo = 1; q.Cc = p.K; q.Rk = q.Sk = 1; q.sh = q.sw = 1; q.pt = q.pl = 0;
   q.fd_HoWo = make_fastdiv(p.M); q.fd_Wo = make_fastdiv(1); q.fd_C = make_fastdiv(p.K); q.fd_S = make_fastdiv(1);
   if (!pipe_eligible<bf16>(q, 1, A_IM2COL, B_NK, vec) || pipe_split_for(q, 1) != 1) return 1;
-  log_gemm<bf16>(p, batch, amode, bmode, 160 + pipe_cfg(q, 1));
+  log_gemm<bf16>(p, batch, amode, bmode, 160 + pipe_cfg(q, 1), pipe_split_logged(q, 1));
   const int st = launch_pipe_auto<A_IM2COL>(q, 1, s);
   if (st) return st;
   const long long items = (long long)p.M * (p.N / 8);
@@ -900,7 +918,7 @@ static int rows_via_im2col(GemmParams& p, int batch, int amode, int bmode, bool 
   q.fd_HoWo = make_fastdiv(p.M); q.fd_Wo = make_fastdiv(1); q.fd_C = make_fastdiv(p.K); q.fd_S = make_fastdiv(1);
   if (!pipe_eligible<bf16>(q, 1, A_IM2COL, B_NK, vec)) return 1;
   if (q.M2 && pipe_split_for(q, 1) != 1) return 1;  // the M2 mask rides in the pipe epilogue only
-  log_gemm<bf16>(p, batch, amode, bmode, 170 + pipe_cfg(q, 1));
+  log_gemm<bf16>(p, batch, amode, bmode, 170 + pipe_cfg(q, 1), pipe_split_logged(q, 1));
   return launch_pipe_auto<A_IM2COL>(q, 1, s);
 }
 
@@ -925,7 +943,8 @@ int dispatch_gemm_impl(GemmParams& p, int batch, int amode, int bmode, bool vec,
   if constexpr (std::is_same<T, bf16>::value) {
     if (pipe_eligible<T>(p, batch, amode, bmode, vec)) {
       log_gemm<T>(p, batch, amode, bmode,
-                  130 + (amode == A_ROW ? (pipe_row_short(p, batch) ? row_short_cfg(p) : 3) : pipe_cfg(p, batch)));
+                  130 + (amode == A_ROW ? (pipe_row_short(p, batch) ? row_short_cfg(p) : 3) : pipe_cfg(p, batch)),
+                  pipe_split_logged(p, batch));
       return amode == A_IM2COL ? launch_pipe_auto<A_IM2COL>(p, batch, s) : launch_pipe_auto<A_ROW>(p, batch, s);
     }
     const int st = rows_via_im2col<T>(p, batch, amode, bmode, vec, s);
