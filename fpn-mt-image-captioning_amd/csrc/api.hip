@@ -527,7 +527,9 @@ static int conv_bwd_filter(const fpnmt_conv_desc* d, const void* x, const void* 
   p.cs_db = db;
   const int V = d->dtype == FPNMT_BF16 ? 8 : 4;
   const bool vec = d->c % V == 0 && d->k % V == 0 && aligned16(x) && aligned16(dz);
+  set_conv_wgrad_entry(true);  // a split LDS-DMA launch may wait for the deferred flush (fpnmt_set_defer_conv_wgrads)
   const int st = run_gemm(d->dtype, p, 1, A_IM2COL_T, B_KN, vec, S(stream));
+  set_conv_wgrad_entry(false);
   if (st || !p.cs_db) return st;  // error, or the kernel folded the column sums
   return fpnmt_bias_grad(d->dtype, pix, d->k, dz, db, stream);
 }

@@ -13,6 +13,14 @@
 // immediate kernel, so the results are bitwise those of immediate mode; a job
 // whose destination overlaps a queued one's starts a new batch (two jobs of
 // one launch never add into the same element).
+//
+// Weight-gradient GEMMs themselves wait in the same queue: the transformer's
+// Dense ones (gemm_wg_jobs_kernel) and, with fpnmt_set_defer_conv_wgrads, the
+// convolutions' split LDS-DMA launches whose slabs lie in the arena
+// (gemm_pipe_wg_jobs_kernel: the launch's own blocks, a few GEMMs per launch
+// and two blocks to a CU). A queued conv GEMM only writes its own slabs and
+// bias partials; the reduce and column-sum jobs queued right behind it carry
+// the ordering, and every run of the queue launches the GEMMs first.
 #include <vector>
 
 #include "gemm_impl.h"
@@ -70,6 +78,7 @@ struct Deferred {
   // queued jobs in issue order; a barrier index starts a new launch
   std::vector<DefDirect> dir;
   std::vector<DefGemmJob> gj;  // deferred weight-gradient GEMMs (launch_gemm_jobs)
+  std::vector<DefConvWg> cw;   // deferred conv weight-gradient GEMMs (launch_wg_jobs)
   std::vector<DefWgrad> wg;
   std::vector<DefColsum> cs;
   std::vector<Range> dst;  // destinations queued since the last flush
@@ -252,10 +261,20 @@ int flush_gemm_jobs(hipStream_t s) {
   return st;
 }
 
-// every queued job, in phase order gemm -> direct -> wgrad -> colsum (jobs
-// of one flush never share a destination: see overlaps())
+// the queued conv weight-gradient GEMMs (slabs and bias partials for the
+// reduce / colsum jobs behind them)
+int flush_conv_jobs(hipStream_t s) {
+  if (g_def.cw.empty()) return 0;
+  const int st = launch_wg_jobs(g_def.cw.data(), (int)g_def.cw.size(), s);
+  g_def.cw.clear();
+  return st;
+}
+
+// every queued job, in phase order gemm -> conv gemm -> direct -> wgrad ->
+// colsum (jobs of one flush never share a destination: see overlaps())
 int flush_queue(hipStream_t s) {
   int st = flush_gemm_jobs(s);
+  if (!st) st = flush_conv_jobs(s);
   if (!st) st = flush_direct(s);
   if (!st) st = flush_wgrad(s);
   if (!st) st = flush_colsum(s);
@@ -338,6 +357,18 @@ int defer_gemm_job(const DefGemmJob& J, hipStream_t s) {
   g_def.gj.push_back(J);
   return 0;
 }
+
+int defer_conv_wg(const DefConvWg& J) {
+  if (!g_def.active) return fail(FPNMT_E_ARG, "defer_conv_wg: no deferred region");
+  g_def.cw.push_back(J);
+  return 0;
+}
+
+static int g_conv_wgrad_classes = 0;
+static bool g_conv_wgrad_entry = false;
+int conv_wgrad_classes() { return g_conv_wgrad_classes; }
+bool conv_wgrad_entry() { return g_conv_wgrad_entry; }
+void set_conv_wgrad_entry(bool on) { g_conv_wgrad_entry = on; }
 
 int defer_touch(const void* lo, const void* hi, hipStream_t s) {
   if (!g_def.active) return 0;
@@ -424,6 +455,7 @@ int fpnmt_defer_begin(void* arena, long long bytes) {
   g_def.active = true;
   g_def.dir.clear();
   g_def.gj.clear();
+  g_def.cw.clear();
   g_def.wg.clear();
   g_def.cs.clear();
   g_def.dst.clear();
@@ -438,5 +470,12 @@ int fpnmt_defer_flush(fpnmt_stream_t stream) {
 }
 
 long long fpnmt_defer_peak_bytes(void) { return g_def.peak; }
+
+int fpnmt_set_defer_conv_wgrads(int classes) {
+  if (classes < 0) return fail(FPNMT_E_ARG, "set_defer_conv_wgrads: negative class mask");
+  if (g_def.active) return fail(FPNMT_E_ARG, "set_defer_conv_wgrads: inside a deferred region");
+  g_conv_wgrad_classes = classes;
+  return 0;
+}
 
 }  // extern "C"

@@ -63,4 +63,60 @@ int launch_gemm_jobs(const DefGemmJob* jobs_in, int n, hipStream_t s) {
   }
   return 0;
 }
+
+// the flush of the deferred conv weight-gradient GEMMs (deferred.hip): per
+// kernel instantiation, longest reduction per block first, WG_JOBS_PER_LAUNCH
+// per launch, each job's blocks from a multiple of 8 (the XCD remap of a
+// block's index within its job, gemm_pipe_wg_jobs_kernel).
+// Ring depths: 128x128 two stages (64 KB, two blocks per CU, as the Dense
+// jobs); 128x64 three (72 KB, two blocks); 64x256 two (80 KB, two blocks);
+// the 128x256 loader-wave tile (1024 threads, registers at the limit) and
+// 256x128 keep their 3-stage ring and one block per CU.
+template <int BM, int BN, int WM, int WN, int NLW, int STAGES, int BPC>
+static int launch_wg_jobs_t(const WgJobs& J, int blocks, hipStream_t s) {
+  hipLaunchKernelGGL((gemm_pipe_wg_jobs_kernel<BM, BN, WM, WN, A_IM2COL_T, NLW, STAGES, BPC>), dim3(blocks),
+                     dim3(64 * (WM * WN + NLW)), 0, s, J);
+  return check_launch("gemm_pipe_wg_jobs_kernel");
+}
+
+int launch_wg_jobs(const DefConvWg* jobs_in, int n, hipStream_t s) {
+  static const int tile[WGJ_CLASSES][2] = {{128, 128}, {128, 64}, {64, 256}, {128, 256}, {256, 128}};
+  for (int cls = 0; cls < WGJ_CLASSES; ++cls) {
+    std::vector<WgJob> jobs;
+    for (int i = 0; i < n; ++i)
+      if (jobs_in[i].cls == cls) jobs.push_back(jobs_in[i].job);
+    std::stable_sort(jobs.begin(), jobs.end(),
+                     [](const WgJob& a, const WgJob& b) { return a.k_per_split > b.k_per_split; });
+    size_t i = 0;
+    while (i < jobs.size()) {
+      WgJobs J{};
+      J.zero = g_split_ws.zero;
+      long long blocks = 0;
+      while (i < jobs.size() && J.n < WG_JOBS_PER_LAUNCH) {
+        WgJob q = jobs[i];
+        const long long nb = (long long)q.tiles_m * q.tiles_n * q.split_k;
+        if (J.n > 0 && blocks + nb > (1LL << 30)) break;
+        q.blk0 = (int)blocks;
+        blocks = (blocks + nb + 7) & ~7LL;
+        J.j[J.n++] = q;
+        ++i;
+      }
+      if (FILE* f = gemm_log()) {
+        std::fprintf(f, "bf16 a=%d b=%d c=0 M=0 N=0 K=0 batch=1 acc=2 split=0 cfg=112 jobs=%d blocks=%lld tile=%dx%d\n",
+                     A_IM2COL_T, B_KN, J.n, blocks, tile[cls][0], tile[cls][1]);
+        std::fflush(f);
+      }
+      int st = 0;
+      switch (cls) {
+        case WGJ_128_128: st = launch_wg_jobs_t<128, 128, 2, 4, 0, 2, 2>(J, (int)blocks, s); break;
+        case WGJ_128_64: st = launch_wg_jobs_t<128, 64, 2, 2, 0, 3, 2>(J, (int)blocks, s); break;
+        case WGJ_64_256: st = launch_wg_jobs_t<64, 256, 1, 4, 0, 2, 2>(J, (int)blocks, s); break;
+        case WGJ_128_256_LW: st = launch_wg_jobs_t<128, 256, 2, 4, 8, 3, 1>(J, (int)blocks, s); break;
+        default: st = launch_wg_jobs_t<256, 128, 4, 2, 0, 3, 1>(J, (int)blocks, s); break;
+      }
+      if (st) return st;
+    }
+  }
+  return 0;
+}
 }  // namespace fpnmt

@@ -194,7 +194,9 @@ static FILE* gemm_log() {
 // Fields appended after cfg= (tools/gemm_shapes.py reads key=value pairs):
 // psplit= the split count of an LDS-DMA pipe launch (cfg 130+ / 160+ / 170+),
 // tm= tn= the tile grid of a pipelined weight-gradient launch (cfg 110, logged
-// after the launch, when split= is its split count too)
+// after the launch, when split= is its split count too; cfg 111: the same
+// launch queued in a deferred region, run by a grouped launch, cfg 112 with
+// jobs= blocks= tile= of that launch)
 template <typename T>
 static void log_gemm(const GemmParams& p, int batch, int amode, int bmode, int cfg, int psplit = 0) {
   if (FILE* f = gemm_log()) {
@@ -202,7 +204,7 @@ static void log_gemm(const GemmParams& p, int batch, int amode, int bmode, int c
                  std::is_same<T, float>::value ? "f32" : "bf16", amode, bmode, p.c_mode, p.M, p.N, p.K, batch,
                  p.accumulate, p.split_k, cfg);
     if (psplit > 0) std::fprintf(f, " psplit=%d", psplit);
-    if (cfg == 110) std::fprintf(f, " tm=%d tn=%d", p.tiles_m, p.tiles_n);
+    if (cfg == 110 || cfg == 111) std::fprintf(f, " tm=%d tn=%d", p.tiles_m, p.tiles_n);
     std::fputc('\n', f);
     std::fflush(f);
   }
@@ -625,6 +627,44 @@ static bool pipe_wg_eligible(const GemmParams& p, int batch, int amode, int bmod
   return kt >= 16;
 }
 
+// The kernel instantiations with a grouped form (gemm_pipe_wg_jobs_kernel;
+// gemm_bf16.hip: launch_wg_jobs holds the ring depth of each), -1: none
+enum { WGJ_128_128 = 0, WGJ_128_64, WGJ_64_256, WGJ_128_256_LW, WGJ_256_128, WGJ_CLASSES };
+template <int AM, int BM, int BN, int WM, int WN, int NLW>
+constexpr int wg_job_class() {
+  if (AM != A_IM2COL_T) return -1;
+  if (BM == 128 && BN == 128 && WM == 2 && WN == 4 && NLW == 0) return WGJ_128_128;
+  if (BM == 128 && BN == 64 && WM == 2 && WN == 2 && NLW == 0) return WGJ_128_64;
+  if (BM == 64 && BN == 256 && WM == 1 && WN == 4 && NLW == 0) return WGJ_64_256;
+  if (BM == 128 && BN == 256 && WM == 2 && WN == 4 && NLW == 8) return WGJ_128_256_LW;
+  if (BM == 256 && BN == 128 && WM == 4 && WN == 2 && NLW == 0) return WGJ_256_128;
+  return -1;
+}
+
+// A split conv weight gradient inside a deferred region whose slabs (and
+// folded bias partials) lie in the arena: queued, run at the flush (the
+// caller holds x and dz until then: fpnmt_set_defer_conv_wgrads). q: the
+// launch's slab params. g_wg_queued tells the dispatcher's log.
+static bool g_wg_queued = false;
+static bool wg_conv_job_ok(const GemmParams& q, int cls) {
+  if (cls < 0 || !conv_wgrad_entry() || !((conv_wgrad_classes() >> cls) & 1) || !defer_active()) return false;
+  if (q.ngroups > 0 || q.split_k <= 1 || !defer_owns(q.C) || (q.cs_part && !defer_owns(q.cs_part))) return false;
+  return q.lda < (1LL << 31) && q.ldb < (1LL << 31) && q.ldc < (1LL << 31);
+}
+static int defer_conv_job(const GemmParams& q, int cls) {
+  DefConvWg J{};
+  WgJob& j = J.job;
+  j.A = q.A; j.B = q.B; j.C = (float*)q.C; j.cs_part = q.cs_part;
+  j.M = q.M; j.N = q.N; j.K = q.K;
+  j.lda = (int)q.lda; j.ldb = (int)q.ldb; j.ldc = (int)q.ldc;
+  j.H = q.H; j.W = q.W; j.Cc = q.Cc; j.Ho = q.Ho; j.Wo = q.Wo; j.Rk = q.Rk; j.Sk = q.Sk;
+  j.sh = q.sh; j.sw = q.sw; j.pt = q.pt; j.pl = q.pl;
+  j.fd_HoWo = q.fd_HoWo; j.fd_Wo = q.fd_Wo; j.fd_C = q.fd_C; j.fd_S = q.fd_S;
+  j.k_per_split = q.k_per_split; j.split_k = q.split_k; j.tiles_m = q.tiles_m; j.tiles_n = q.tiles_n;
+  J.cls = cls;
+  return defer_conv_wg(J);
+}
+
 template <int AM, int BM, int BN, int WM, int WN, int NLW = 0>
 static int launch_pipe_wg_t(GemmParams& p, hipStream_t s) {
   constexpr int BK = 64;
@@ -675,9 +715,16 @@ static int launch_pipe_wg_t(GemmParams& p, hipStream_t s) {
   };
   if (p.split_k > 1) {
     const GemmParams q = slab_params(p, 1, base);
-    hipLaunchKernelGGL((gemm_pipe_wg_kernel<BM, BN, WM, WN, AM, 0, 32, NLW>), grid, dim3(64 * (WM * WN + NLW)), 0, s,
-                       q);
-    int st = check_launch("gemm_pipe_wg_kernel");
+    int st;
+    constexpr int cls = wg_job_class<AM, BM, BN, WM, WN, NLW>();
+    if (wg_conv_job_ok(q, cls)) {  // the same blocks, in a grouped launch at the flush
+      st = defer_conv_job(q, cls);
+      g_wg_queued = true;
+    } else {
+      hipLaunchKernelGGL((gemm_pipe_wg_kernel<BM, BN, WM, WN, AM, 0, 32, NLW>), grid, dim3(64 * (WM * WN + NLW)), 0,
+                         s, q);
+      st = check_launch("gemm_pipe_wg_kernel");
+    }
     if (!st) st = launch_wgrad_reduce(p, 1, base, s);
     return st ? st : fold_bias();
   }
@@ -952,8 +999,9 @@ int dispatch_gemm_impl(GemmParams& p, int batch, int amode, int bmode, bool vec,
   }
   if constexpr (std::is_same<T, bf16>::value) {
     if (pipe_wg_eligible(p, batch, amode, bmode, vec)) {
+      g_wg_queued = false;
       const int st = amode == A_IM2COL_T ? launch_pipe_wg<A_IM2COL_T>(p, s) : launch_pipe_wg<A_COL>(p, s);
-      log_gemm<T>(p, batch, amode, bmode, 110);
+      log_gemm<T>(p, batch, amode, bmode, g_wg_queued ? 111 : 110);  // 111: queued for a grouped launch (cfg 112)
       return st;
     }
   }

@@ -40,8 +40,9 @@ inline FastDiv make_fastdiv(uint32_t d) {
   f.m = (uint32_t)(((((uint64_t)1) << 32) * ((((uint64_t)1) << l) - d)) / d + 1);
   return f;
 }
-// exact for n < 2^31
-__device__ __forceinline__ uint32_t fdiv(uint32_t n, const FastDiv& f) {
+// exact for n < 2^31 (F: FastDiv, in registers or in the kernel-argument segment)
+template <class F>
+__device__ __forceinline__ uint32_t fdiv(uint32_t n, const F& f) {
   return (__umulhi(n, f.m) + n) >> f.s;
 }
 
@@ -1312,5 +1313,41 @@ struct DefGemmJob {
 constexpr int GEMM_JOBS_PER_LAUNCH = 32;
 int defer_gemm_job(const DefGemmJob& J, hipStream_t s);                     // deferred.hip (queues)
 int launch_gemm_jobs(const DefGemmJob* jobs, int n, hipStream_t s);         // gemm_bf16.hip
+
+// Deferred conv weight gradients: a split LDS-DMA weight-gradient launch
+// (gemm_pipe_wg_kernel) of a convolution whose slabs lie in the deferred arena
+// is queued instead of launched and runs at the flush in grouped launches of
+// its own kernel instantiation (`cls`, gemm_dispatch.h: wg_job_class), ahead
+// of the slab reduces and column sums queued behind it.
+// A queued conv weight gradient (deferred.hip; gemm_pipe_wg_jobs_kernel): what
+// the kernel body reads of a split, ungrouped launch's GemmParams, and the
+// job's first block in its grouped launch. C is the slab base (ldc = N, split
+// y at y * M * N floats); 168 B, so 20 jobs stay within 4 KB of kernel
+// arguments.
+struct WgJob {
+  const void* A;
+  const void* B;
+  float* C;
+  float* cs_part;
+  int M, N, K;
+  int lda, ldb, ldc;
+  int H, W, Cc, Ho, Wo, Rk, Sk, sh, sw, pt, pl;
+  FastDiv fd_HoWo, fd_Wo, fd_C, fd_S;
+  int k_per_split, split_k, tiles_m, tiles_n;
+  int blk0;
+};
+static_assert(sizeof(WgJob) <= 168, "20 jobs within 4 KB of kernel arguments");
+struct DefConvWg {
+  WgJob job;
+  int cls;
+};
+int defer_conv_wg(const DefConvWg& J);                                       // deferred.hip (queues)
+int launch_wg_jobs(const DefConvWg* jobs, int n, hipStream_t s);             // gemm_bf16.hip
+// the classes (bit 1 << cls) whose conv weight gradients may be queued
+// (fpnmt_set_defer_conv_wgrads), and whether the running call is a conv
+// weight-gradient entry point whose caller keeps x and dz alive to the flush
+int conv_wgrad_classes();
+bool conv_wgrad_entry();
+void set_conv_wgrad_entry(bool on);
 
 }  // namespace fpnmt

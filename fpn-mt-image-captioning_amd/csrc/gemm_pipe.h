@@ -902,9 +902,36 @@ constexpr bool wg_cs_ok() {
   return MF == 32 && wg_stages(64 * (BM + BN) * 2) * 64 * (BM + BN) * 2 + 64 * WM * WN * (BN / WN / 32) * 4 <= 160 * 1024;
 }
 
-template <int BM, int BN, int WM, int WN, int AM, int SPREAD = 0, int MF = 32, int NLW = 0>
-__global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(const GemmParams p) {
+// The body reads a whole launch's GemmParams in place in the kernel-argument
+// segment (KernargGemmParams: scalar loads where a field is used; through a
+// reference to the kernel's by-value copy the compiler loads the whole struct
+// at entry and spills ~90 SGPRs), a job's WgJob from the block's registers.
+typedef const __attribute__((address_space(4))) GemmParams KernargGemmParams;
+template <class P> struct wg_is_job { static constexpr bool value = false; };
+template <> struct wg_is_job<WgJob> { static constexpr bool value = true; };
+template <> struct wg_is_job<const WgJob> { static constexpr bool value = true; };
+// field-wise copies (no copy constructor binds a kernel-argument lvalue)
+template <class F>
+__device__ __forceinline__ FastDiv wg_ld_fd(const F& f) { return FastDiv{f.d, f.m, f.s}; }
+template <class G>
+__device__ __forceinline__ GemmGroup wg_ld_group(const G& g) {
+  return GemmGroup{g.A, g.B, g.C, g.R, g.M, g.K, g.start, g.H, g.W, g.Ho, g.Wo, wg_ld_fd(g.fd_HoWo), wg_ld_fd(g.fd_Wo)};
+}
+// the slab stride: c_split of the launch; a job's slabs are whole M x N
+template <class P>
+__device__ __forceinline__ long long wg_c_split(const P& p) {
+  if constexpr (wg_is_job<P>::value) return (long long)p.M * p.N;
+  else return p.c_split;
+}
+
+// The kernel body: `bx` is the block's index within its GEMM (the launch's
+// blockIdx.x, or the block's offset in its job of a grouped launch), `zero`
+// >= 256 B of zeros. P = KernargGemmParams (every form) or WgJob (split,
+// ungrouped: slab stores only). STAGES: the ring depth.
+template <int BM, int BN, int WM, int WN, int AM, int SPREAD, int MF, int NLW, int STAGES, class P>
+__device__ __forceinline__ void gemm_pipe_wg_body(const P& p, const int bx, const void* zero_page) {
   typedef bf16 T;
+  constexpr bool FULL = !wg_is_job<P>::value;  // k-groups and the one-split atomic store
   static_assert(NLW == 0 || SPREAD == 0, "the loader waves issue the whole tile");
   constexpr int NC = 64 * WM * WN;             // MFMA threads
   constexpr int NT = NLW ? 64 * NLW : NC;      // DMA-issuing threads
@@ -921,8 +948,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(cons
   constexpr int CA = BM / 8, CB = BN / 8;            // 16-B chunks per row
   constexpr int NA = BK * (BM / 8) / NT, NB = BK * (BN / 8) / NT;  // DMA chunks per thread per stage
   static_assert(NA * NT == BK * (BM / 8) && NB * NT == BK * (BN / 8), "");
-  // 256x256 (64 KB per stage): a 2-stage ring
-  constexpr int STAGES = wg_stages(STAGE_BYTES);
+  static_assert(STAGES >= 2 && STAGES <= wg_stages(STAGE_BYTES), "ring depth");
   // the folded bias column sums (p.cs_part) per MFMA thread in LDS behind the
   // ring (registers are at the limit in the 16-wave form), where they fit
   // beside the same ring (wg_cs_ok; the host folds only there)
@@ -940,7 +966,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(cons
   // work items, i.e. all tiles of (about) one split, so the split's slices of
   // x and dz are fetched into that XCD's L2 once and re-read from there
   const int ntile = p.tiles_m * p.tiles_n;
-  const int w = xcd_remap(blockIdx.x, ntile * p.split_k);
+  const int w = xcd_remap(bx, ntile * p.split_k);
   const int split = w / ntile;
   const int bid = w - split * ntile;
   const int tmi = bid / p.tiles_n;
@@ -951,20 +977,21 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(cons
   // may run over several groups; every K-tile belongs to exactly one group.
   const int M = p.M, N = p.N;
   const int m0 = tmi * BM, n0 = tni * BN;
-  const T* zero = (const T*)p.zero16;
-  int tot_kt;
+  const T* zero = (const T*)zero_page;
+  const long long c_split = wg_c_split(p);
+  int tot_kt = (p.K + BK - 1) / BK;
+  if constexpr (FULL) {
   if (p.ngroups > 0) {
     tot_kt = 0;
 #pragma unroll
     for (int q = 0; q < MAX_GROUPS; ++q)
       if (q < p.ngroups) tot_kt = p.groups[q].start + (p.groups[q].K + BK - 1) / BK;
-  } else {
-    tot_kt = (p.K + BK - 1) / BK;
+  }
   }
   const int kt_per = p.k_per_split / BK;
   const int kt0 = split * kt_per;
   const int nk = max(0, min(kt_per, tot_kt - kt0));
-  if (nk <= 0 && !p.c_split && !p.cs_part) return;  // empty split adds nothing (a slab gets its zeros below)
+  if (nk <= 0 && !c_split && !p.cs_part) return;  // empty split adds nothing (a slab gets its zeros below)
   // ---- per-thread DMA chunks: row (k within the tile) and logical chunk ----
   // chunk q = i*NT + tid lands at LDS byte q*16 of the image: row q>>4, slot
   // q&15, holding logical 8-element chunk (slot ^ ((row & 3) << 2)).
@@ -1008,17 +1035,19 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(cons
   auto tile_src = [&](int kt) {
     // this K-tile's group (uniform: scalar selects over the kernarg groups)
     const int vkt = kt0 + kt;
-    WgSrc ws{(const T*)p.A, (const T*)p.B, p.K, 0, p.H, p.W, p.Ho, p.Wo, p.fd_HoWo, p.fd_Wo};
+    WgSrc ws{(const T*)p.A, (const T*)p.B, p.K, 0, p.H, p.W, p.Ho, p.Wo, wg_ld_fd(p.fd_HoWo), wg_ld_fd(p.fd_Wo)};
     int t0 = 0;
+    if constexpr (FULL) {
     if (p.ngroups > 0) {
-      GemmGroup G = p.groups[0];
+      GemmGroup G = wg_ld_group(p.groups[0]);
 #pragma unroll
       for (int q = 1; q < MAX_GROUPS; ++q)
-        if (q < p.ngroups && vkt >= p.groups[q].start) G = p.groups[q];
+        if (q < p.ngroups && vkt >= p.groups[q].start) G = wg_ld_group(p.groups[q]);
       ws.Ag = (const T*)G.A; ws.Bg = (const T*)G.B;
       ws.K = G.K; t0 = G.start;
       ws.gH = G.H; ws.gW = G.W; ws.gHo = G.Ho; ws.gWo = G.Wo;
       ws.fdHoWo = G.fd_HoWo; ws.fdWo = G.fd_Wo;
+    }
     }
     ws.k0 = (vkt - t0) * BK;  // first reduction row of the tile within its group
     return ws;
@@ -1220,7 +1249,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(cons
     // lane: row m0 + wm WTM + 16 a + (l & 15), columns n0 + wn WTN + 16 b +
     // 4 (l >> 4) .. +3
     const bool vec = (N & 3) == 0 && (p.ldc & 3) == 0;
-    float* slab = p.c_split ? Cg + (long long)split * p.c_split : nullptr;
+    float* slab = c_split ? Cg + (long long)split * c_split : nullptr;
 #pragma unroll
     for (int a = 0; a < TM; ++a) {
       const int row = m0 + wm * WTM + a * 16 + (lane & 15);
@@ -1234,7 +1263,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(cons
           if (vec) *(f32x4*)dst = acc[a][b];
           else
             for (int j = 0; j < 4 && col + j < N; ++j) dst[j] = acc[a][b][j];
-        } else {  // one split: a single fp32 atomic per element (one adder, any order)
+        } else if constexpr (FULL) {  // one split: a single fp32 atomic per element (one adder, any order)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             if (col + j < N)
@@ -1244,10 +1273,10 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(cons
       }
     }
   } else {
-  if (p.c_split) {
+  if (c_split) {
     // deterministic split-K: raw partials into this split's slab (plain
     // stores), summed in split order by wgrad_reduce_kernel
-    float* slab = Cg + (long long)split * p.c_split;
+    float* slab = Cg + (long long)split * c_split;
 #pragma unroll
     for (int a = 0; a < TM; ++a)
 #pragma unroll
@@ -1263,6 +1292,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(cons
     return;
   }
   // one split: a single fp32 atomic per element (one adder, any order)
+  if constexpr (FULL) {
 #pragma unroll
   for (int a = 0; a < TM; ++a) {
 #pragma unroll
@@ -1278,7 +1308,54 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(cons
     }
   }
   }
+  }
 }
+
+template <int BM, int BN, int WM, int WN, int AM, int SPREAD = 0, int MF = 32, int NLW = 0>
+__global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_wg_kernel(const GemmParams p) {
+  // 256x256 (64 KB per stage): a 2-stage ring. p is the kernel's only argument
+  KernargGemmParams& kp = *(KernargGemmParams*)__builtin_amdgcn_kernarg_segment_ptr();
+  gemm_pipe_wg_body<BM, BN, WM, WN, AM, SPREAD, MF, NLW, wg_stages(64 * (BM + BN) * 2)>(kp, (int)blockIdx.x,
+                                                                                       kp.zero16);
+}
+
+// Grouped form (the queued conv weight gradients of a backward, deferred.hip):
+// one launch over the block lists of up to WG_JOBS_PER_LAUNCH split GEMMs of
+// this instantiation laid end to end (job q owns blocks blk0 .. blk0 + tiles *
+// split_k - 1; blk0 is a multiple of 8 so the XCD remap of a block's index
+// within its job sees the launch's XCD round-robin, and the few blocks past a
+// job's last exit). Each block runs gemm_pipe_wg_body on its job: the tiles,
+// split boundaries, K order, slab layout and folded bias partials of the
+// job's own launch, bit for bit. STAGES < the immediate kernel's ring lets two
+// blocks share a CU, each hiding the other's prologue, DMA latency and slab
+// store (128x128: 2 stages = 64 KB).
+constexpr int WG_JOBS_PER_LAUNCH = 20;
+struct WgJobs {
+  WgJob j[WG_JOBS_PER_LAUNCH];
+  const void* zero;
+  int n;
+};
+static_assert(sizeof(WgJobs) <= 4096, "kernel arguments");
+
+// BPC: the blocks per CU the ring depth was chosen for (registers allocated
+// so that BPC blocks' waves fit the SIMDs).
+template <int BM, int BN, int WM, int WN, int AM, int NLW, int STAGES, int BPC>
+__global__ __launch_bounds__(64 * (WM * WN + NLW), BPC * (WM * WN + NLW) / 4) void gemm_pipe_wg_jobs_kernel(
+    const WgJobs J) {
+  static_assert(BPC * (STAGES * 64 * (BM + BN) * 2 +
+                       (wg_cs_ok<BM, BN, WM, WN, 32>() ? 64 * WM * WN * (BN / WN / 32) * 4 : 0)) <= 160 * 1024,
+                "BPC blocks' rings in LDS");
+  // this block's job: static selects over the kernarg table (no dynamic
+  // index into the kernarg struct)
+  WgJob G = J.j[0];
+#pragma unroll
+  for (int q = 1; q < WG_JOBS_PER_LAUNCH; ++q)
+    if (q < J.n && (int)blockIdx.x >= J.j[q].blk0) G = J.j[q];
+  const int local = (int)blockIdx.x - G.blk0;
+  if (local >= G.tiles_m * G.tiles_n * G.split_k) return;  // padding up to the next job's blk0
+  gemm_pipe_wg_body<BM, BN, WM, WN, AM, 0, 32, NLW, STAGES>(G, local, J.zero);
+}
+
 
 
 // ---------------------------------------------------------------------------

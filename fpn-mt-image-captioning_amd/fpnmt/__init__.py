@@ -37,6 +37,16 @@ class _Config:
     # slabs, bias / LayerNorm column sums) queued and run as a few batched
     # launches at its end (fpnmt_defer_begin / _flush; the TrainEngine)
     defer_reductions = True
+    # ... and, inside such a region, the convolutions' split LDS-DMA weight-
+    # gradient GEMMs themselves (fpnmt_set_defer_conv_wgrads): queued with x
+    # and dz held (L.defer_keep) and run at the flush as grouped launches of
+    # their own blocks (gemm_pipe_wg_jobs_kernel), a few GEMMs per launch and
+    # two blocks to a CU on a shallower LDS ring, instead of one one-wave
+    # launch each. Bitwise the immediate gradients (same tiles, splits and K
+    # order; test_gpu_wgrad_jobs.py). True: the tile classes of
+    # _lib.CONV_WGRAD_CLASSES_DEFAULT; an int: a class mask; False: every
+    # conv weight gradient launches immediately
+    defer_conv_wgrads = True
     # single-graph step (one GPU): the transformer's clip + AMSGrad runs on a
     # second stream as soon as the transformer's backward is complete, beside
     # the feature extractor's backward; the feature extractor's part follows

@@ -161,6 +161,7 @@ SIGNATURES = {
     "fpnmt_conv2d_bwd_data_mask": [C.POINTER(ConvDesc), P, P, P, I, P, I, P],
     "fpnmt_conv2d_bwd_data_res": [C.POINTER(ConvDesc), P, P, P, P, P],
     "fpnmt_conv2d_bwd_data_res_act": [C.POINTER(ConvDesc), P, P, P, P, P, I, P],
+    "fpnmt_set_defer_conv_wgrads": [I],
     "fpnmt_conv2d_bwd_filter": [C.POINTER(ConvDesc), P, P, P, P, P],
     "fpnmt_conv2d_bwd_filter_bias": [C.POINTER(ConvDesc), P, P, P, P, P, P],
     "fpnmt_conv2d_fwd_grouped": [C.POINTER(ConvDesc), I, C.POINTER(ConvLevel), P, P, P, P],
@@ -341,9 +342,13 @@ class deferred_reductions:
                 buf = torch.empty(DEFER_BYTES, dtype=torch.uint8, device=f"cuda:{dev}")
                 _defer[dev] = buf
             _ensure_workspace()
+            from . import config
+            classes = conv_wgrad_classes(config.defer_conv_wgrads)
+            check(lib.fpnmt_set_defer_conv_wgrads(classes), "fpnmt_set_defer_conv_wgrads")
             check(lib.fpnmt_defer_begin(buf.data_ptr(), buf.numel()), "fpnmt_defer_begin")
             self.on = True
             _defer_active[0] = True
+            _defer_conv[0] = classes != 0
         return self
 
     def __exit__(self, *exc):
@@ -357,6 +362,30 @@ class deferred_reductions:
 
 
 _defer_active = [False]
+_defer_conv = [False]  # the active region queues conv weight-gradient GEMMs
+
+# kernel instantiations of the conv weight gradient with a grouped form (bit
+# 1 << class, csrc/gemm_dispatch.h: WGJ_*): 128x128, 128x64, 64x256, the
+# 128x256 loader-wave tile, 256x128. The default is what the C2 step measured
+# (profiles/wgrad_jobs/ab.txt): the first three on a shallower ring with two
+# blocks per CU, the loader-wave tile on its own ring (one block per CU: it
+# gains from the grouped launch alone); no single-level conv of that step
+# reaches 256x128, which stays immediate
+CONV_WGRAD_CLASSES_DEFAULT = 0b01111
+
+
+def conv_wgrad_classes(setting):
+    """config.defer_conv_wgrads -> the class mask of fpnmt_set_defer_conv_wgrads:
+    False 0, True the measured default, an int that mask (experiments)."""
+    if setting is True:
+        return CONV_WGRAD_CLASSES_DEFAULT
+    return int(setting or 0)
+
+
+def defer_conv_wgrads():
+    """Inside deferred_reductions with conv weight gradients queued: the
+    caller of a conv weight-gradient launch holds x and dz until the flush."""
+    return _defer_active[0] and _defer_conv[0]
 _defer_keep = []  # tensors read by queued launches (fpnmt_bias_grad), held until the flush
 
 

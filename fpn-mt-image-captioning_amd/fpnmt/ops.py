@@ -77,8 +77,9 @@ def _wgrad(fn, *keep, conv=False):
     filling idle CUs)."""
     sd = _side
     if not sd.active or (conv and sd.mode != "all"):
-        if not conv:
-            # inside deferred_reductions a Dense weight gradient is queued and
+        if not conv or L.defer_conv_wgrads():
+            # inside deferred_reductions a Dense weight gradient (and, with
+            # config.defer_conv_wgrads, a convolution's split one) is queued and
             # run at the flush (grouped launches): its operands must live until then
             for t in keep:
                 L.defer_keep(t)

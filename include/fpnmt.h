@@ -102,6 +102,17 @@ int fpnmt_set_workspace(void* ws, long long bytes);
 int fpnmt_defer_begin(void* arena, long long bytes);
 int fpnmt_defer_flush(fpnmt_stream_t stream);
 long long fpnmt_defer_peak_bytes(void);
+/* Conv weight-gradient GEMMs in the deferred queue. classes: bit mask of the
+ * LDS-DMA weight-gradient tile classes (bit 0 128x128, 1 128x64, 2 64x256,
+ * 3 128x256 with loader waves, 4 256x128); 0 (the default): none. While a bit
+ * is set, a split (split-K > 1) launch of that class made by
+ * fpnmt_conv2d_bwd_filter / _bias inside a deferred region, whose slabs fit
+ * the arena, is queued and runs at the flush in grouped launches, ahead of its
+ * queued slab reduce: THE CALLER KEEPS x AND dz ALIVE AND UNCHANGED UNTIL THE
+ * FLUSH. The gradients are bitwise those of the immediate launches. Not
+ * queued: the grouped (multi-level) entry points, unsplit launches, the other
+ * kernels, slabs that fell back to the workspace. Set outside a region.    */
+int fpnmt_set_defer_conv_wgrads(int classes);
 
 /* ---- general batched GEMM on MFMA (Dense layers, attention products) ---
  * C[z] = epilogue(alpha * op(A[z]) @ op(B[z]))  for z in [0, batch)

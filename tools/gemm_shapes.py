@@ -22,12 +22,16 @@ CFG = {0: "128x128x64", 1: "64x64x32", 2: "64x64x64", 3: "128x128x32", 4: "32x32
 log = [dict(kv.split("=") for kv in ln.split()[1:]) for ln in open(sys.argv[1]) if ln.strip()]
 # deferred weight-gradient GEMMs (cfg 150) are queued, not launched: they run
 # at the flush as grouped gemm_wg_jobs_kernel launches, reported separately
-jobs_log = [g for g in log if g["cfg"] == "150"]
-log = [g for g in log if g["cfg"] != "150"]
+# (likewise the queued conv weight gradients, cfg 111, run by the grouped
+# gemm_pipe_wg_jobs_kernel launches that cfg 112 lines record)
+QUEUED = ("150", "111", "112")
+jobs_log = [g for g in log if g["cfg"] in ("150", "111")]
+log = [g for g in log if g["cfg"] not in QUEUED]
 rows = list(csv.DictReader(open(sys.argv[2])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-jobs_k = [r for r in rows if "gemm_wg_jobs_kernel" in r["Kernel_Name"]]
-rows_nojobs = [r for r in rows if "gemm_wg_jobs_kernel" not in r["Kernel_Name"]]
+JOBS_KERNELS = ("gemm_wg_jobs_kernel", "gemm_pipe_wg_jobs_kernel")
+jobs_k = [r for r in rows if any(k in r["Kernel_Name"] for k in JOBS_KERNELS)]
+rows_nojobs = [r for r in rows if not any(k in r["Kernel_Name"] for k in JOBS_KERNELS)]
 # a split small GEMM is two launches (partials + reduce): the reduce's time is
 # charged to the GEMM launch before it
 gemm = []
