@@ -210,6 +210,8 @@ SIGNATURES = {
     "fpnmt_beam_step": [I, I, I, P, LL, P, P, P, I, I, P, P, I, I, P, P, I, P, P, P],
     "fpnmt_beam_step_log": [I, I, I, P, LL, P, P, P, P, P, I, I, P, P, I, I, P, P, P],
     "fpnmt_beam_finalize": [I, I, P, I, P, P, P, F, P, I, P, P, P],
+    "fpnmt_sample_step": [I, I, P, LL, F, I, F, ULL, P, P, P, P, P, I, I, I, P, P, P],
+    "fpnmt_sample_uniform": [I, I, ULL, P, P, P],
     "fpnmt_bn_stats": [I, LL, I, P, P, P, P, P, F, P],
     "fpnmt_bn_apply": [I, LL, I, P, P, P, P, P, F, I, P, P, P],
     "fpnmt_bn_bwd": [I, LL, I, P, P, P, P, F, I, P, P, P, P, P, P],
@@ -258,6 +260,7 @@ lib = _load()
 
 
 E_ARG, E_UNSUPPORTED, E_HIP = -1, -2, -3  # include/fpnmt.h status codes
+SAMPLE_FILTER_MAX_VOCAB = 16384  # FPNMT_SAMPLE_FILTER_MAX_VOCAB
 
 
 def check(status: int, what: str = ""):

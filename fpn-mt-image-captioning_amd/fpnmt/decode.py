@@ -32,6 +32,8 @@ rule of the step (fpnmt_beam_step_log) and how the result is chosen
     finished (its rows are then frozen while other images decode on);
   * the n-best list ranks the beams by score / len^length_alpha (len counts
     the final <end>; alpha 0: the raw sum), ties to the lower beam.
+SampleDecoder draws captions instead (fpnmt_sample_step: temperature, top-k,
+nucleus) on the same cache, attention and graphs; its rows never re-rank.
 """
 from __future__ import annotations
 
@@ -53,16 +55,13 @@ def _gemm(m, n, k, dt, a, lda, b, c, ldc, bias, s):
     call("fpnmt_gemm", g, a, b, c, None, bias, None, s)
 
 
-class BeamDecoder:
-    """decode(images) -> list of token-id lists, one per image; in
-    mode="beam", decode(images, n_best=k) -> per image the k best
-    (token ids, score) pairs, best first."""
+class _CachedDecoder:
+    """What BeamDecoder and SampleDecoder share: the geometry, the encoder
+    pass with every layer's cross K/V, the staged biases, and one decode
+    position through embed -> layers -> fp32 logits on the K/V cache.
+    `beam_n` is the number of rows per image."""
 
-    def __init__(self, transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph=True,
-                 mode="reference", length_alpha=0.0):
-        if mode not in ("reference", "beam"):
-            raise ValueError(f"mode must be 'reference' or 'beam', got {mode!r}")
-        self.mode, self.length_alpha = mode, float(length_alpha)
+    def __init__(self, transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph=True):
         self.tr = transformer
         dec = transformer.decoder
         self.n_images, self.beam_n, self.T = n_images, beam_n, max_seq_len
@@ -80,40 +79,9 @@ class BeamDecoder:
         self.graphs = None
         self.qkv_bias = []
 
-    # ---------------------------------------------------------- buffers
-    def _alloc(self, dev):
-        dt, R, T, d = self.dt, self.R, self.T, self.d
-        self.kv = torch.empty((max(self.L, 1), R, T, 2 * d), dtype=dt, device=dev)
-        self.hist = [torch.empty((R, T + 1), dtype=torch.int32, device=dev) for _ in range(2)]
-        self.src = [torch.empty((R, T), dtype=torch.int32, device=dev) for _ in range(2)]
-        self.tok = torch.empty(R, dtype=torch.int32, device=dev)
-        self.prob = torch.empty(R, dtype=torch.float32, device=dev)
-        self.result = torch.zeros((self.n_images, T), dtype=torch.int32, device=dev)
-        self.result_len = torch.zeros(self.n_images, dtype=torch.int32, device=dev)
-        self.status = torch.zeros(self.n_images, dtype=torch.int32, device=dev)
-        if self.mode == "beam":
-            n, K = self.n_images, self.beam_n
-            self.score = torch.empty(R, dtype=torch.float32, device=dev)
-            self.blen = torch.zeros(R, dtype=torch.int32, device=dev)
-            self.fin = torch.zeros(R, dtype=torch.int32, device=dev)
-            self.nbest_tok = torch.zeros((n, K, T), dtype=torch.int32, device=dev)
-            self.nbest_len = torch.zeros((n, K), dtype=torch.int32, device=dev)
-            self.nbest_score = torch.zeros((n, K), dtype=torch.float32, device=dev)
-
-    def _reset(self):
-        R = self.R
-        self.tok.fill_(self.start_token)
-        if self.mode == "beam":
-            self.score.fill_(float("-inf"))
-            self.score.view(self.n_images, self.beam_n)[:, 0] = 0.0
-            self.blen.zero_()
-            self.fin.zero_()
-        else:
-            self.prob.fill_(1.0)
-        self.hist[0][:, 0] = self.start_token
-        self.src[0][:, 0] = torch.arange(R, dtype=torch.int32, device=self.tok.device)
-        self.result_len.zero_()
-        self.status.zero_()
+    def _alloc_cache(self, dev):
+        self.kv = torch.empty((max(self.L, 1), self.R, self.T, 2 * self.d), dtype=self.dt, device=dev)
+        self.tok = torch.empty(self.R, dtype=torch.int32, device=dev)
 
     # ------------------------------------------------------------- encoder
     def _encode(self, images):
@@ -160,13 +128,29 @@ class BeamDecoder:
                 self.graphs = None
             self.qkv_bias[i].copy_(b)
 
-    # ---------------------------------------------------------------- step
-    def _step(self, t):
+    def _prepare(self, images):
+        """Before the first position of a decode call: buffers for the
+        compute dtype, the encoder side, the state reset, the step graphs."""
+        dt = compute_dtype()
+        if self.dt != dt:
+            self.dt = dt
+            self._alloc(images.device)
+            self.enc_kv = None
+            self.graphs = None
+        self._encode(images)
+        self._stage_biases(images.device)
+        self._reset()
+        if self.use_graph and self.graphs is None:
+            self._capture()
+
+    # ------------------------------------------------------------ position
+    def _logits(self, t, src):
+        """Position t of every row: embed self.tok, the decoder layers on the
+        K/V cache, the fp32 logits (R, V). src: the rows' cache-row tables
+        (None: every row reads its own cache row)."""
         tr, dec = self.tr, self.tr.decoder
         dt, code, R, T, d = self.dt, dtype_code(self.dt), self.R, self.T, self.d
         s = stream_ptr()
-        hin, hout = self.hist[t % 2], self.hist[(t + 1) % 2]
-        sin, sout = self.src[t % 2], self.src[(t + 1) % 2]
         x = torch.empty((R, d), dtype=dt, device=self.tok.device)
         pe = dec.pos_encoding
         call("fpnmt_embed_posenc_fwd", code, R, 1, d, ptr(self.tok), ptr(dec.embedding.embeddings),
@@ -185,7 +169,7 @@ class BeamDecoder:
                   bias.data_ptr() + d * bias.element_size(), s)
             a = torch.empty((R, d), dtype=dt, device=x.device)
             call("fpnmt_decode_attention", code, R, self.heads, self.depth, t + 1, scale, ptr(q), d, ptr(kvl),
-                 T * 2 * d, 2 * d, 0, d, ptr(sin), T, 1, ptr(a), d, s)
+                 T * 2 * d, 2 * d, 0, d, ptr(src), T, 1, ptr(a), d, s)
             out1 = lay.layernorm1(lay.mha1.dense(a), residual=x)
             q2 = lay.mha2.wq(out1)
             a2 = torch.empty((R, d), dtype=dt, device=x.device)
@@ -195,7 +179,73 @@ class BeamDecoder:
                  d, s)
             out2 = lay.layernorm2(lay.mha2.dense(a2), residual=out1)
             x = lay.layernorm3(lay.ffn2(lay.ffn1(out2)), residual=out2)
-        logits = tr.final_layer(x)  # (R, V) fp32
+        return tr.final_layer(x)  # (R, V) fp32
+
+    def _capture(self):
+        """One graph per position t (the step's shapes depend on t). The
+        first step runs eagerly to build compute copies / workspaces; the
+        state it advances is reset before the graphs are replayed."""
+        from .train import capture_sequence
+        self._step(0)
+        torch.cuda.synchronize()
+        graphs = capture_sequence([(lambda t=t: self._step(t)) for t in range(self.T)])
+        self.graphs = graphs
+        self._reset()
+
+
+class BeamDecoder(_CachedDecoder):
+    """decode(images) -> list of token-id lists, one per image; in
+    mode="beam", decode(images, n_best=k) -> per image the k best
+    (token ids, score) pairs, best first."""
+
+    def __init__(self, transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph=True,
+                 mode="reference", length_alpha=0.0):
+        if mode not in ("reference", "beam"):
+            raise ValueError(f"mode must be 'reference' or 'beam', got {mode!r}")
+        self.mode, self.length_alpha = mode, float(length_alpha)
+        super().__init__(transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph)
+
+    # ---------------------------------------------------------- buffers
+    def _alloc(self, dev):
+        dt, R, T, d = self.dt, self.R, self.T, self.d
+        self._alloc_cache(dev)
+        self.hist = [torch.empty((R, T + 1), dtype=torch.int32, device=dev) for _ in range(2)]
+        self.src = [torch.empty((R, T), dtype=torch.int32, device=dev) for _ in range(2)]
+        self.prob = torch.empty(R, dtype=torch.float32, device=dev)
+        self.result = torch.zeros((self.n_images, T), dtype=torch.int32, device=dev)
+        self.result_len = torch.zeros(self.n_images, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(self.n_images, dtype=torch.int32, device=dev)
+        if self.mode == "beam":
+            n, K = self.n_images, self.beam_n
+            self.score = torch.empty(R, dtype=torch.float32, device=dev)
+            self.blen = torch.zeros(R, dtype=torch.int32, device=dev)
+            self.fin = torch.zeros(R, dtype=torch.int32, device=dev)
+            self.nbest_tok = torch.zeros((n, K, T), dtype=torch.int32, device=dev)
+            self.nbest_len = torch.zeros((n, K), dtype=torch.int32, device=dev)
+            self.nbest_score = torch.zeros((n, K), dtype=torch.float32, device=dev)
+
+    def _reset(self):
+        R = self.R
+        self.tok.fill_(self.start_token)
+        if self.mode == "beam":
+            self.score.fill_(float("-inf"))
+            self.score.view(self.n_images, self.beam_n)[:, 0] = 0.0
+            self.blen.zero_()
+            self.fin.zero_()
+        else:
+            self.prob.fill_(1.0)
+        self.hist[0][:, 0] = self.start_token
+        self.src[0][:, 0] = torch.arange(R, dtype=torch.int32, device=self.tok.device)
+        self.result_len.zero_()
+        self.status.zero_()
+
+    # ---------------------------------------------------------------- step
+    def _step(self, t):
+        T = self.T
+        s = stream_ptr()
+        hin, hout = self.hist[t % 2], self.hist[(t + 1) % 2]
+        sin, sout = self.src[t % 2], self.src[(t + 1) % 2]
+        logits = self._logits(t, sin)
         if self.mode == "beam":
             call("fpnmt_beam_step_log", self.n_images, self.beam_n, self.V, ptr(logits), self.V, ptr(self.score),
                  ptr(self.blen), ptr(self.fin), ptr(hin), ptr(hout), T + 1, t, ptr(sin), ptr(sout), T,
@@ -216,17 +266,7 @@ class BeamDecoder:
         if n_best < 1 or n_best > (self.beam_n if self.mode == "beam" else 1):
             raise ValueError(f"n_best {n_best}: mode {self.mode!r} with {self.beam_n} beams gives 1.."
                              f"{self.beam_n if self.mode == 'beam' else 1}")
-        dt = compute_dtype()
-        if self.dt != dt:
-            self.dt = dt
-            self._alloc(images.device)
-            self.enc_kv = None
-            self.graphs = None
-        self._encode(images)
-        self._stage_biases(images.device)
-        self._reset()
-        if self.use_graph and self.graphs is None:
-            self._capture()
+        self._prepare(images)
         steps = 0
         for t in range(self.T):
             if self.graphs is not None:
@@ -254,13 +294,86 @@ class BeamDecoder:
             return [tok[i, 0, :lens[i][0]].tolist() for i in range(n)]
         return [[(tok[i, k, :lens[i][k]].tolist(), score[i][k]) for k in range(n_best)] for i in range(n)]
 
-    def _capture(self):
-        """One graph per position t (the step's shapes depend on t). The
-        first step runs eagerly to build compute copies / workspaces; the
-        state it advances is reset before the graphs are replayed."""
-        from .train import capture_sequence
-        self._step(0)
-        torch.cuda.synchronize()
-        graphs = capture_sequence([(lambda t=t: self._step(t)) for t in range(self.T)])
-        self.graphs = graphs
-        self._reset()
+
+class SampleDecoder(_CachedDecoder):
+    """Draws n_samples captions per image from the model's distribution on
+    the machinery of BeamDecoder: the same K/V cache, decode attention and
+    per-position graphs; the last launch of a step is fpnmt_sample_step
+    (temperature, top-k, nucleus) instead of a ranking. Rows never re-rank,
+    so every row reads its own cache row (no src tables) and one history
+    table is updated in place. The uniforms are a function of (seed, row,
+    position): the seed lives in a device word the graphs read, so replays
+    draw new captions without a re-capture.
+
+    decode(images, seed=None) -> per image n_samples pairs (token ids without
+    <start> and a final <end>, log-probability under the model at temperature
+    1, unfiltered), in sample order."""
+
+    def __init__(self, transformer, n_images, n_samples, max_seq_len, start_token, end_token, use_graph=True,
+                 temperature=1.0, top_k=0, top_p=1.0):
+        if n_samples < 1:
+            raise ValueError(f"n_samples must be >= 1, got {n_samples}")
+        if not (temperature > 0.0 and math.isfinite(temperature)):
+            raise ValueError(f"temperature must be a finite positive number, got {temperature!r}")
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"top_p must lie in (0, 1], got {top_p!r}")
+        if int(top_k) != top_k or top_k < 0:
+            raise ValueError(f"top_k must be an integer >= 0 (0: off), got {top_k!r}")
+        if max_seq_len > 65536:
+            raise ValueError(f"max_seq_len {max_seq_len}: the draw counter holds positions below 65536")
+        self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
+        super().__init__(transformer, n_images, n_samples, max_seq_len, start_token, end_token, use_graph)
+        filtered = 0 < self.top_k < self.V or self.top_p < 1.0
+        if filtered and self.V > L.SAMPLE_FILTER_MAX_VOCAB:
+            raise ValueError(f"top_k / top_p need a vocabulary of at most {L.SAMPLE_FILTER_MAX_VOCAB}, got {self.V}")
+        self.n_samples = n_samples
+        self._calls = 0
+
+    def _alloc(self, dev):
+        R, T = self.R, self.T
+        self._alloc_cache(dev)
+        self.hist = torch.empty((R, T + 1), dtype=torch.int32, device=dev)
+        self.score = torch.empty(R, dtype=torch.float32, device=dev)
+        self.slen = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.fin = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.seed_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def _reset(self):
+        self.tok.fill_(self.start_token)
+        self.hist[:, 0] = self.start_token
+        self.score.zero_()
+        self.slen.zero_()
+        self.fin.zero_()
+
+    def _step(self, t):
+        logits = self._logits(t, None)
+        call("fpnmt_sample_step", self.R, self.V, ptr(logits), self.V, self.temperature, self.top_k, self.top_p, 0,
+             ptr(self.seed_dev), ptr(self.score), ptr(self.slen), ptr(self.fin), ptr(self.hist), self.T + 1, t,
+             self.end_token, ptr(self.tok), None, stream_ptr())
+
+    @torch.no_grad()
+    def decode(self, images, seed=None, check_every=8):
+        """images (n_images, H, W, 3) on the GPU -> per image a list of
+        n_samples (token-id list, log-probability) pairs. seed None: a
+        counter that advances per call; the same seed gives the same draws."""
+        if images.shape[0] != self.n_images:
+            raise ValueError(f"expected {self.n_images} images, got {images.shape[0]}")
+        if seed is None:
+            seed = self._calls
+        self._calls += 1
+        self._prepare(images)
+        self.seed_dev.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        for t in range(self.T):
+            if self.graphs is not None:
+                self.graphs[t].replay()
+            else:
+                self._step(t)
+            if check_every and (t + 1) % check_every == 0 and t + 1 < self.T and bool(self.fin.all()):
+                break
+        hist, lens = self.hist.tolist(), self.slen.tolist()
+        fin, score = self.fin.tolist(), self.score.tolist()
+        out = []
+        for i in range(self.n_images):
+            rows = range(i * self.n_samples, (i + 1) * self.n_samples)
+            out.append([(hist[r][1:1 + lens[r] - fin[r]], score[r]) for r in rows])
+        return out

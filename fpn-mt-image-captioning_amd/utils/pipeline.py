@@ -138,7 +138,7 @@ class Pipeline:
 
     @torch.no_grad()
     def predict_batch(self, images, max_seq_len=None, beam_n=BEAM_SEARCH_N, use_graph=True, mode="reference",
-                      length_alpha=0.0, n_best=1):
+                      length_alpha=0.0, n_best=1, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None):
         """predict() for a batch of images (n, h, w, 3) at once: the same
         beam procedure per image (pipeline.py:82-154), with a K/V cache and a
         hipGraph per decode step (fpnmt.decode.BeamDecoder). Returns one
@@ -148,9 +148,24 @@ class Pipeline:
         beam search proper on the same machinery: beams scored by their sum
         of log-probabilities, finished beams kept, the result ranked by
         score / len^length_alpha. n_best > 1 then returns, per image, the
-        n_best (token-id list, score) pairs, best first."""
-        from fpnmt.decode import BeamDecoder
+        n_best (token-id list, score) pairs, best first.
+
+        mode="sample" draws n_samples captions per image from the model
+        (fpnmt.decode.SampleDecoder: temperature, top_k (0: off), top_p (1:
+        off); seed None: a counter per decoder, a given seed repeats its
+        draws) and returns, per image, n_samples (token-id list,
+        log-probability) pairs in sample order; beam_n, length_alpha and
+        n_best do not apply."""
+        from fpnmt.decode import BeamDecoder, SampleDecoder
         T = max_seq_len or self.max_seq_len
+        if mode == "sample":
+            key = (images.shape[0], n_samples, T, use_graph, mode, float(temperature), top_k, float(top_p))
+            dec = getattr(self, "_decoders", {}).get(key)
+            if dec is None:
+                dec = SampleDecoder(self.transformer, images.shape[0], n_samples, T, self.start_token, self.end_token,
+                                    use_graph=use_graph, temperature=temperature, top_k=top_k, top_p=top_p)
+                self.__dict__.setdefault("_decoders", {})[key] = dec
+            return dec.decode(images, seed=seed)
         key = (images.shape[0], beam_n, T, use_graph, mode, float(length_alpha))
         dec = getattr(self, "_decoders", {}).get(key)
         if dec is None:

@@ -21,6 +21,7 @@
  *   fpnmt_decode_attention scaled_dot_product_attention, last query row   utils/pipeline.py:105-113
  *   fpnmt_beam_step        softmax + top_k + gather + argmax of predict   utils/pipeline.py:115-147
  *   fpnmt_beam_step_log, fpnmt_beam_finalize   beam search proper (log-prob beams, n-best)   not in the reference
+ *   fpnmt_sample_step, fpnmt_sample_uniform    sampled decoding (temperature, top-k, top-p)    not in the reference
  *
  * Conventions (all functions):
  *   - Return 0 on success or a negative FPNMT_E* code; never throw across the ABI.
@@ -693,6 +694,48 @@ int fpnmt_beam_step_log(int n_images, int beam_n, int vocab, const float* logits
 int fpnmt_beam_finalize(int n_images, int beam_n, const int32_t* hist, int hist_ld, const float* beam_score,
                         const int32_t* beam_len, const int32_t* beam_fin, float alpha, int32_t* nbest_tok,
                         int tok_ld, int32_t* nbest_len, float* nbest_score, fpnmt_stream_t stream);
+
+/* Sampled decoding (not in the reference): the last launch of a decode step
+ * that draws one token per row from its fp32 logits. Rows are independent
+ * (no re-ranking: no src tables, hist is updated in place). State per row:
+ * score (fp32 sum of log-probabilities), slen (tokens after <start>, a final
+ * <end> counted), fin (0 / 1).
+ * fpnmt_sample_step, live row r (fin[r] == 0):
+ *   weights  w_j = exp((l_j - max l) / temperature); a -inf logit weighs 0.
+ *     Sums run on q_j = trunc(w_j * 2^40) as integers: exact in any order, so
+ *     the kept set and the token are a function of the logits and u alone; a
+ *     weight below 2^-40 of the maximum counts as 0.
+ *   top_k > 0: keep the tokens whose logit is >= the top_k-th largest logit
+ *     of the row (every token equal to that boundary is kept; -0 == +0);
+ *     top_k == 0 or >= vocab: off.
+ *   top_p < 1: of those, by weight descending, the shortest prefix whose
+ *     weight is >= top_p * (their total weight), and every token whose logit
+ *     equals the last kept one; top_p == 1: off. The maximum is always kept.
+ *   draw     u = uniform01(key, ((uint64)r << 16) | t) (csrc/common.h), key =
+ *     seed + (seed_dev ? *seed_dev * 0x9E3779B97F4A7C15 : 0) as for dropout:
+ *     a replayed graph draws anew when the host changes the device word. The
+ *     token is the smallest kept index whose prefix sum of kept weights, in
+ *     index order, exceeds u * W (W the kept total); it always has w > 0.
+ *   writes   tok_out[r] = hist[r][t+1] = token; score[r] += l_token -
+ *     logsumexp(l) (temperature 1, unfiltered: the model's log-probability);
+ *     slen[r] = t + 1; fin[r] = (token == end_token); kept_out[r] (may be
+ *     NULL) = size of the kept set.
+ * Finished row: logits not read; hist[r][t+1] = tok_out[r] = end_token,
+ *   kept_out[r] = 0, score / slen / fin unchanged.
+ * Row with no drawable token (a NaN or +inf logit, or all -inf): token
+ *   end_token, fin = 1, score = -inf, slen = t + 1, kept_out = 0.
+ * Requires temperature finite > 0, 0 < top_p <= 1, top_k >= 0, 0 <=
+ * end_token < vocab <= ldl, 0 <= t < 65536, hist_ld >= t + 2; with a filter
+ * on, vocab <= FPNMT_SAMPLE_FILTER_MAX_VOCAB (the row is staged in 64 KB of
+ * LDS), else FPNMT_E_UNSUPPORTED.
+ * fpnmt_sample_uniform: u_out[r] = the u row r would use at step t.         */
+#define FPNMT_SAMPLE_FILTER_MAX_VOCAB 16384
+int fpnmt_sample_step(int rows, int vocab, const float* logits, long long ldl, float temperature, int top_k,
+                      float top_p, unsigned long long seed, const long long* seed_dev, float* score, int32_t* slen,
+                      int32_t* fin, int32_t* hist, int hist_ld, int t, int end_token, int32_t* tok_out,
+                      int32_t* kept_out /* may be NULL */, fpnmt_stream_t stream);
+int fpnmt_sample_uniform(int rows, int t, unsigned long long seed, const long long* seed_dev, float* u_out,
+                         fpnmt_stream_t stream);
 
 /* ---- MobileNetV2 backbone (models/mobilenet.py:43-72 ->
  * keras MobileNetV2(alpha=1.0), models/retinanet.py:274) -------------------
