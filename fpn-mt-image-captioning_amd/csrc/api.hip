@@ -2,6 +2,7 @@
 // implicit-GEMM convolution (fwd / bwd-data / bwd-filter) and attention
 // (QK^T -> masked row softmax -> PV, and its backward), plus error handling.
 #include "gemm_impl.h"
+#include <cstdlib>
 #include <cstring>
 
 namespace fpnmt {
@@ -19,6 +20,22 @@ int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(FPNMT_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
   return 0;
+}
+FILE* gemm_log() {
+  static FILE* f = [] {
+    const char* path = std::getenv("FPNMT_GEMM_LOG");
+    return path ? std::fopen(path, "a") : nullptr;
+  }();
+  return f;
+}
+void log_attn(const char* op, const char* kernel, int dtype, int b, int h, int lq, int lk, int d, int n_views) {
+  if (FILE* f = gemm_log()) {
+    std::fprintf(f, "attn op=%s kernel=%s dtype=%s b=%d h=%d lq=%d lk=%d d=%d", op, kernel,
+                 dtype == FPNMT_BF16 ? "bf16" : "f32", b, h, lq, lk, d);
+    if (n_views >= 0) std::fprintf(f, " n=%d", n_views);
+    std::fputc('\n', f);
+    std::fflush(f);
+  }
 }
 
 __global__ void zero2d_kernel(char* __restrict__ p, size_t pitch, size_t width, size_t rows) {
@@ -828,6 +845,7 @@ int fpnmt_attention_fwd(const fpnmt_attn_desc* d, const void* q, const void* k, 
   hipStream_t s = S(stream);
   if (attn_q1_ok(d)) return attn_q1_fwd(d, q, k, v, mask, out, weights, s);
   if (attn_small_ok(d)) return attn_small_fwd(d, q, k, v, mask, out, weights, s);
+  log_attn("fwd", "general", d);
   const int B = d->b, H = d->h, Lq = d->lq, Lk = d->lk, D = d->d;
   const long long ldw = d->ldw;
   float* Sbuf = (float*)ws;
@@ -876,16 +894,19 @@ int fpnmt_attention_fwd(const fpnmt_attn_desc* d, const void* q, const void* k, 
 
 // n views sharing b / h / scale, all one-query bf16 D = 64 without a mask:
 // one grouped launch; anything else: the views one by one
-static bool views_grouped(int n, const fpnmt_attn_desc* d, const float* const* mask) {
-  if (n <= 0) return false;
-  for (int i = 0; i < n; ++i)
-    if ((mask && mask[i]) || d[i].b != d[0].b || d[i].h != d[0].h || d[i].scale != d[0].scale) return false;
-  return true;
-}
-
 // a view without images or queries has nothing to compute (the single-view
 // entries return at once); the grouped launch takes the others
 static bool view_empty(const fpnmt_attn_desc& d) { return d.b == 0 || d.lq == 0; }
+
+static bool views_grouped(int n, const fpnmt_attn_desc* d, const float* const* mask) {
+  int first = -1;  // the empty views take no part: they neither launch nor have to share b / h / scale
+  for (int i = 0; i < n; ++i) {
+    if (view_empty(d[i])) continue;
+    if (first < 0) first = i;
+    if ((mask && mask[i]) || d[i].b != d[first].b || d[i].h != d[first].h || d[i].scale != d[first].scale) return false;
+  }
+  return first >= 0;
+}
 
 int fpnmt_attention_fwd_views(int n, const fpnmt_attn_desc* d, const void* const* q, const void* const* k,
                               const void* const* v, const float* const* mask, void* const* out,
@@ -906,6 +927,7 @@ int fpnmt_attention_fwd_views(int n, const fpnmt_attn_desc* d, const void* const
     gd[ng] = d[i]; gq[ng] = q[i]; gk[ng] = k[i]; gv[ng] = v[i]; go[ng] = out[i]; gw[ng] = weights[i];
     ++ng;
   }
+  if (ng > 0 && !grouped) log_attn("views_fwd", "per_view", &d[0], n);
   if (grouped && ng > 0) {
     const int e = attn_q1_views_fwd(ng, gd, gq, gk, gv, go, gw, S(stream));
     if (e) return e;
@@ -941,6 +963,7 @@ int fpnmt_attention_bwd_views(int n, const fpnmt_attn_desc* d, const void* const
     gdq[ng] = dq[i]; gdk[ng] = dk[i]; gdv[ng] = dv[i];
     ++ng;
   }
+  if (ng > 0 && !grouped) log_attn("views_bwd", "per_view", &d[0], n);
   if (grouped && ng > 0) {
     const int e = attn_q1_views_bwd(ng, gd, gq, gk, gv, gw, gdo, gdq, gdk, gdv, S(stream));
     if (e) return e;
@@ -970,6 +993,7 @@ int fpnmt_attention_bwd(const fpnmt_attn_desc* d, const void* q, const void* k, 
   if (Lq == 0 || Lk == 0) {
     // no scores: dq = 0, dk/dv over empty key set or no queries -> zero
     // rows of all batches share one pitch (row b*L+i at base + (b*L+i)*ld): one 2D memset each
+    log_attn("bwd", "zero_fill", d);
     if (Lq > 0 && zero_fill_2d(dq, d->ldq * esz, (size_t)H * D * esz, (size_t)B * Lq, s))
       return fail(FPNMT_E_HIP, "attention_bwd: zero dq");
     if (Lk > 0 && (zero_fill_2d(dk, d->ldk * esz, (size_t)H * D * esz, (size_t)B * Lk, s) ||
@@ -979,6 +1003,7 @@ int fpnmt_attention_bwd(const fpnmt_attn_desc* d, const void* q, const void* k, 
   }
   if (attn_q1_ok(d)) return attn_q1_bwd(d, q, k, v, weights, d_out, dq, dk, dv, s);
   if (attn_small_ok(d)) return attn_small_bwd(d, q, k, v, weights, d_out, dq, dk, dv, s);
+  log_attn("bwd", "general", d);
   // 1) dP = dO V^T (fp32)
   {
     GemmParams p;

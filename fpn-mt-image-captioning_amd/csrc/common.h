@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdio>
 #include <string>
 #include "../../include/fpnmt.h"
 
@@ -16,6 +17,15 @@ namespace fpnmt {
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
 int check_launch(const char* what);
+// FPNMT_GEMM_LOG=<file> (api.hip): the launch log, opened once per process;
+// null when the variable is unset. One line per GEMM launch (log_gemm,
+// gemm_dispatch.h) and one per attention launcher:
+//   attn op=<fwd|bwd|views_fwd|views_bwd|decode> kernel=<name> dtype=<f32|bf16> b= h= lq= lk= d= [n=<views>]
+FILE* gemm_log();
+void log_attn(const char* op, const char* kernel, int dtype, int b, int h, int lq, int lk, int d, int n_views = -1);
+inline void log_attn(const char* op, const char* kernel, const fpnmt_attn_desc* d, int n_views = -1) {
+  log_attn(op, kernel, d->dtype, d->b, d->h, d->lq, d->lk, d->d, n_views);
+}
 // Zero fills as kernels (api.hip). hipMemsetAsync / hipMemset2DAsync inside a
 // captured hipGraph were measured NOT to re-zero on replay (tools/probes/
 // conv_noise.py: the strided 1x1 bwd-data accumulated onto stale memory), so

@@ -1289,11 +1289,14 @@ int attn_q1_fwd(const fpnmt_attn_desc* d, const void* q, const void* k, const vo
   const dim3 grid(d->b, d->h);
   if (d->dtype == FPNMT_BF16 && d->d == 64 && d->lk >= Q1_MW_MIN_LK && q1_vec(d, k, v, out)) {
     const size_t sm = (size_t)(64 + 2 * Q1_MW + 64 * Q1_MW + d->lk) * sizeof(float);
+    log_attn("fwd", "q1_mw", d);
     hipLaunchKernelGGL((attn_q1_fwd_mw_kernel<Q1_MW>), grid, dim3(64 * Q1_MW), sm, s, d->h, d->lk, d->scale,
                        (const bf16*)q, d->ldq, (const bf16*)k, d->ldk, (const bf16*)v, d->ldv, mask, d->m_sb, d->m_sh,
                        d->m_sj, (bf16*)out, d->ldo, (bf16*)weights, d->ldw);
   } else if (d->dtype == FPNMT_BF16) {
-    if (q1_vec(d, k, v, out))
+    const bool vec = q1_vec(d, k, v, out);
+    log_attn("fwd", vec ? (d->d == 64 ? "q1_vec64" : "q1_vec") : "q1_scalar", d);
+    if (vec)
       hipLaunchKernelGGL((attn_q1_fwd_kernel<bf16, true>), grid, dim3(64), smem, s, d->h, d->lk, d->d, d->scale,
                          (const bf16*)q, d->ldq, (const bf16*)k, d->ldk, (const bf16*)v, d->ldv, mask, d->m_sb,
                          d->m_sh, d->m_sj, (bf16*)out, d->ldo, (bf16*)weights, d->ldw);
@@ -1302,6 +1305,7 @@ int attn_q1_fwd(const fpnmt_attn_desc* d, const void* q, const void* k, const vo
                          (const bf16*)q, d->ldq, (const bf16*)k, d->ldk, (const bf16*)v, d->ldv, mask, d->m_sb,
                          d->m_sh, d->m_sj, (bf16*)out, d->ldo, (bf16*)weights, d->ldw);
   } else {
+    log_attn("fwd", "q1_scalar", d);
     hipLaunchKernelGGL((attn_q1_fwd_kernel<float, false>), grid, dim3(64), smem, s, d->h, d->lk, d->d, d->scale,
                        (const float*)q, d->ldq, (const float*)k, d->ldk, (const float*)v, d->ldv, mask, d->m_sb,
                        d->m_sh, d->m_sj, (float*)out, d->ldo, (float*)weights, d->ldw);
@@ -1315,11 +1319,14 @@ int attn_q1_bwd(const fpnmt_attn_desc* d, const void* q, const void* k, const vo
   const dim3 grid(d->b, d->h);
   if (d->dtype == FPNMT_BF16 && d->d == 64 && d->lk >= Q1_MW_MIN_LK && q1_vec(d, k, v, dq, dk, dv)) {
     const size_t sm = (size_t)(64 + 2 * Q1_MW + 64 * Q1_MW + 2 * d->lk) * sizeof(float);
+    log_attn("bwd", "q1_mw", d);
     hipLaunchKernelGGL((attn_q1_bwd_mw_kernel<Q1_MW>), grid, dim3(64 * Q1_MW), sm, s, d->h, d->lk, d->scale,
                        (const bf16*)q, d->ldq, (const bf16*)k, d->ldk, (const bf16*)v, d->ldv, (const bf16*)weights,
                        d->ldw, (const bf16*)dout, d->ldo, (bf16*)dq, (bf16*)dk, (bf16*)dv);
   } else if (d->dtype == FPNMT_BF16) {
-    if (q1_vec(d, k, v, dq, dk, dv))
+    const bool vec = q1_vec(d, k, v, dq, dk, dv);
+    log_attn("bwd", vec ? (d->d == 64 ? "q1_vec64" : "q1_vec") : "q1_scalar", d);
+    if (vec)
       hipLaunchKernelGGL((attn_q1_bwd_kernel<bf16, true>), grid, dim3(64), smem, s, d->h, d->lk, d->d, d->scale,
                          (const bf16*)q, d->ldq, (const bf16*)k, d->ldk, (const bf16*)v, d->ldv,
                          (const bf16*)weights, d->ldw, (const bf16*)dout, d->ldo, (bf16*)dq, (bf16*)dk, (bf16*)dv);
@@ -1328,6 +1335,7 @@ int attn_q1_bwd(const fpnmt_attn_desc* d, const void* q, const void* k, const vo
                          (const bf16*)q, d->ldq, (const bf16*)k, d->ldk, (const bf16*)v, d->ldv,
                          (const bf16*)weights, d->ldw, (const bf16*)dout, d->ldo, (bf16*)dq, (bf16*)dk, (bf16*)dv);
   } else {
+    log_attn("bwd", "q1_scalar", d);
     hipLaunchKernelGGL((attn_q1_bwd_kernel<float, false>), grid, dim3(64), smem, s, d->h, d->lk, d->d, d->scale,
                        (const float*)q, d->ldq, (const float*)k, d->ldk, (const float*)v, d->ldv,
                        (const float*)weights, d->ldw, (const float*)dout, d->ldo, (float*)dq, (float*)dk, (float*)dv);
@@ -1372,6 +1380,7 @@ int attn_q1_views_fwd(int n, const fpnmt_attn_desc* d, const void* const* q, con
     a.lk = d[j].lk;
   }
   const size_t sm = (size_t)(64 + 2 * Q1_MW + 64 * Q1_MW + max_lk) * sizeof(float);
+  log_attn("views_fwd", "views_grouped", FPNMT_BF16, d[0].b, d[0].h, 1, max_lk, 64, n);  // lk: the longest view
   hipLaunchKernelGGL((attn_q1_views_fwd_kernel<Q1_MW>), dim3(d[0].b, d[0].h, n), dim3(64 * Q1_MW), sm, s, A, d[0].h,
                      d[0].scale);
   return check_launch("attention_q1_views_fwd");
@@ -1393,6 +1402,7 @@ int attn_q1_views_bwd(int n, const fpnmt_attn_desc* d, const void* const* q, con
     a.lk = d[j].lk;
   }
   const size_t sm = (size_t)(64 + 2 * Q1_MW + 64 * Q1_MW + 2 * max_lk) * sizeof(float);
+  log_attn("views_bwd", "views_grouped", FPNMT_BF16, d[0].b, d[0].h, 1, max_lk, 64, n);  // lk: the longest view
   hipLaunchKernelGGL((attn_q1_views_bwd_kernel<Q1_MW>), dim3(d[0].b, d[0].h, n), dim3(64 * Q1_MW), sm, s, A, d[0].h,
                      d[0].scale);
   return check_launch("attention_q1_views_bwd");
@@ -1417,6 +1427,8 @@ int fpnmt_decode_attention(int dtype, int rows, int heads, int depth, int lk, fl
   const bool v16 = depth == 64 && ((uintptr_t)q & 15) == 0 && (ldq & 7) == 0 && ((uintptr_t)kv & 15) == 0 &&
                    ((row_stride | pos_stride | k_off | v_off) & 7) == 0 && ((uintptr_t)out & 15) == 0 &&
                    (ldo & 7) == 0;
+  log_attn("decode", dtype == FPNMT_BF16 && v16 ? (lk <= 16 ? "dec_v2" : "dec_v4") : "dec_scalar", dtype, rows, heads, 1,
+           lk, depth);
   // tools/dec_attn_bench.hip (profiles/r06/dec_attn.txt): 2 positions per lane
   // at 8 waves per SIMD up to lk 16, 4 per lane (96 VGPRs) above
   if (dtype == FPNMT_BF16 && v16 && lk <= 16)
@@ -2048,11 +2060,13 @@ bool attn_small_ok(const fpnmt_attn_desc* d) {
 int attn_small_fwd(const fpnmt_attn_desc* d, const void* q, const void* k, const void* v, const float* mask, void* out,
                    void* weights, hipStream_t s) {
   const dim3 grid(d->b, d->h);
-  if (d->d == 64 && small_vec(d, {q, k, v, out, weights}))
+  const bool vec = small_vec(d, {q, k, v, out, weights});
+  log_attn("fwd", vec ? (d->d == 64 ? "small_mfma" : "small_vec") : "small_scalar", d);
+  if (d->d == 64 && vec)
     hipLaunchKernelGGL(attn_small_fwd_mfma_kernel, grid, dim3(64), 0, s, d->h, d->lq, d->lk, d->scale,
                        (const bf16*)q, d->ldq, (const bf16*)k, d->ldk, (const bf16*)v, d->ldv, mask, d->m_sb, d->m_sh,
                        d->m_si, d->m_sj, (bf16*)out, d->ldo, (bf16*)weights, d->ldw);
-  else if (small_vec(d, {q, k, v, out, weights}))
+  else if (vec)
     hipLaunchKernelGGL(attn_small_fwd_vec_kernel, grid, dim3(256), 0, s, d->h, d->lq, d->lk, d->d, d->scale,
                        (const bf16*)q, d->ldq, (const bf16*)k, d->ldk, (const bf16*)v, d->ldv, mask, d->m_sb, d->m_sh,
                        d->m_si, d->m_sj, (bf16*)out, d->ldo, (bf16*)weights, d->ldw);
@@ -2070,11 +2084,13 @@ int attn_small_fwd(const fpnmt_attn_desc* d, const void* q, const void* k, const
 int attn_small_bwd(const fpnmt_attn_desc* d, const void* q, const void* k, const void* v, const void* weights,
                    const void* dout, void* dq, void* dk, void* dv, hipStream_t s) {
   const dim3 grid(d->b, d->h);
-  if (d->d == 64 && small_vec(d, {q, k, v, weights, dout, dq, dk, dv}))
+  const bool vec = small_vec(d, {q, k, v, weights, dout, dq, dk, dv});
+  log_attn("bwd", vec ? (d->d == 64 ? "small_mfma" : "small_vec") : "small_scalar", d);
+  if (d->d == 64 && vec)
     hipLaunchKernelGGL(attn_small_bwd_mfma_kernel, grid, dim3(64), 0, s, d->h, d->lq, d->lk, d->scale,
                        (const bf16*)q, d->ldq, (const bf16*)k, d->ldk, (const bf16*)v, d->ldv, (const bf16*)weights,
                        d->ldw, (const bf16*)dout, d->ldo, (bf16*)dq, (bf16*)dk, (bf16*)dv);
-  else if (small_vec(d, {q, k, v, weights, dout, dq, dk, dv}))
+  else if (vec)
     hipLaunchKernelGGL(attn_small_bwd_vec_kernel, grid, dim3(256), 0, s, d->h, d->lq, d->lk, d->d, d->scale,
                        (const bf16*)q, d->ldq, (const bf16*)k, d->ldk, (const bf16*)v, d->ldv, (const bf16*)weights,
                        d->ldw, (const bf16*)dout, d->ldo, (bf16*)dq, (bf16*)dk, (bf16*)dv);

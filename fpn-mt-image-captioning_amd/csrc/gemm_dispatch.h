@@ -181,15 +181,8 @@ static int choose_cfg(int amode, int bmode, int M, int N, int K, long long batch
   return deep ? CFG_64_64_64 : CFG_64_64_32;
 }
 
-// FPNMT_GEMM_LOG=<file>: one line per launch (shape, modes, tile config),
-// joined with a rocprofv3 kernel trace by tools/gemm_shapes.py
-static FILE* gemm_log() {
-  static FILE* f = [] {
-    const char* path = std::getenv("FPNMT_GEMM_LOG");
-    return path ? std::fopen(path, "a") : nullptr;
-  }();
-  return f;
-}
+// FPNMT_GEMM_LOG=<file> (gemm_log(), common.h): one line per launch (shape,
+// modes, tile config), joined with a rocprofv3 kernel trace by tools/gemm_shapes.py
 
 // Fields appended after cfg= (tools/gemm_shapes.py reads key=value pairs):
 // psplit= the split count of an LDS-DMA pipe launch (cfg 130+ / 160+ / 170+),
