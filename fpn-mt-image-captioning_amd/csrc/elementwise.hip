@@ -825,14 +825,39 @@ __device__ __forceinline__ int ln_col(int lane, int k) {
 // Rows wid, wid + nw, ... of one LayerNorm (block blk of nblk); op > 0: the
 // output is dropout(y) with the mask of fpnmt_dropout on the (rows, d) tensor
 // (key, element r * d + col), applied to the stored dtype value.
-template <typename T, bool VEC>
+//
+// SYN (the one-key cross-attention sublayer, fpnmt_layernorm_bcast_fwd): x is
+// not read but synthesised from the per-image fp32 row c[r / sy.t] (+ cbias)
+// under the dropout mask of the Dense GEMM epilogue that would have stored it.
+struct LnSynth {
+  const float* c;
+  const float* cbias;
+  int t;
+  float p;
+  unsigned long long key;
+};
+template <typename T>
+__device__ __forceinline__ float ln_synth(const LnSynth& sy, float sc, long long r, long long crow, int d, int col) {
+#pragma clang fp contract(off)
+  float a = sy.c[crow * d + col];
+  if (sy.cbias) a += sy.cbias[col];
+  if (sy.p > 0.f) a = uniform01(sy.key, (uint64_t)r * (uint64_t)d + (uint64_t)col) >= sy.p ? a * sc : 0.f;
+  return to_f32(from_f32<T>(a));
+}
+
+template <typename T, bool VEC, bool SYN = false>
 __device__ __forceinline__ void ln_fwd_rows(long long blk, long long nblk, long long rows, int d, float eps,
                                             const T* __restrict__ x, const T* __restrict__ res,
                                             const float* __restrict__ gamma, const float* __restrict__ beta,
                                             const float* __restrict__ pe, int pe_rows, T* __restrict__ y,
                                             float* __restrict__ mean_out, float* __restrict__ rstd_out, float op,
-                                            unsigned long long okey) {
+                                            unsigned long long okey, const LnSynth sy = LnSynth{},
+                                            T* __restrict__ x_out = nullptr) {
+  // every instantiation (x read or synthesised, vector or scalar columns)
+  // rounds alike: no implicit contraction, the fused steps are written out
+#pragma clang fp contract(off)
   const int lane = threadIdx.x & 63;
+  const float ssc = SYN && sy.p > 0.f ? 1.f / (1.f - sy.p) : 1.f;
   const long long wid = (blk * 256LL + threadIdx.x) >> 6;
   const long long nw = nblk * 4;
   const float osc = op > 0.f ? 1.f / (1.f - op) : 1.f;
@@ -863,19 +888,26 @@ __device__ __forceinline__ void ln_fwd_rows(long long blk, long long nblk, long 
         const int c0 = (lane + 64 * i) * 8;
         bf16x8 xv = {}, rv = {};
         if (c0 < d) {
-          xv = *(const bf16x8*)(x + r * d + c0);
+          if constexpr (!SYN) xv = *(const bf16x8*)(x + r * d + c0);
           if (res) rv = *(const bf16x8*)(res + r * d + c0);
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           float t = 0.f;
           if (c0 < d) {
-            t = to_f32(xv[e]);
+            if constexpr (SYN) {
+              t = ln_synth<T>(sy, ssc, r, r / sy.t, d, c0 + e);
+              xv[e] = from_f32<T>(t);
+            } else {
+              t = to_f32(xv[e]);
+            }
             if (res) t = to_f32(from_f32<T>(t + to_f32(rv[e])));
           }
           v[i * 8 + e] = t;
           s += t;
         }
+        if constexpr (SYN)
+          if (x_out && c0 < d) *(bf16x8*)(x_out + r * d + c0) = xv;
       }
     } else {
 #pragma unroll
@@ -883,7 +915,13 @@ __device__ __forceinline__ void ln_fwd_rows(long long blk, long long nblk, long 
         const int col = lane + 64 * i;
         v[i] = 0.f;
         if (col < d) {
-          float t = to_f32(x[r * d + col]);
+          float t;
+          if constexpr (SYN) {
+            t = ln_synth<T>(sy, ssc, r, r / sy.t, d, col);
+            if (x_out) x_out[r * d + col] = from_f32<T>(t);
+          } else {
+            t = to_f32(x[r * d + col]);
+          }
           if (res) t = to_f32(from_f32<T>(t + to_f32(res[r * d + col])));
           v[i] = t;
           s += t;
@@ -895,7 +933,7 @@ __device__ __forceinline__ void ln_fwd_rows(long long blk, long long nblk, long 
 #pragma unroll
     for (int i = 0; i < LN_MAXE; ++i) {
       const int col = ln_col<VEC>(lane, i);
-      if (col < d) { const float t = v[i] - mu; q += t * t; }
+      if (col < d) { const float t = v[i] - mu; q = __builtin_fmaf(t, t, q); }
     }
     const float var = wave_sum(q) / (float)d;
     const float rs = rsqrtf(var + eps);
@@ -907,7 +945,7 @@ __device__ __forceinline__ void ln_fwd_rows(long long blk, long long nblk, long 
           bf16x8 ov;
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
-            float o = (v[i * 8 + e] - mu) * rs * gm[i * 8 + e] + bt[i * 8 + e];
+            float o = __builtin_fmaf((v[i * 8 + e] - mu) * rs, gm[i * 8 + e], bt[i * 8 + e]);
             if (pe) o += pv[i * 8 + e];
             ov[e] = from_f32<T>(o);
             if (op > 0.f)
@@ -922,7 +960,7 @@ __device__ __forceinline__ void ln_fwd_rows(long long blk, long long nblk, long 
       for (int i = 0; i < LN_MAXE; ++i) {
         const int col = lane + 64 * i;
         if (col < d) {
-          float o = (v[i] - mu) * rs * gm[i] + bt[i];
+          float o = __builtin_fmaf((v[i] - mu) * rs, gm[i], bt[i]);
           if (pe) o += pv[i];
           T ot = from_f32<T>(o);
           if (op > 0.f)
@@ -957,15 +995,18 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(long long rows, int d, floa
 // dx, bit for bit): dz = keep(row * d + col) ? dx / (1 - p) : 0. ip > 0: dy
 // is first the backward of a dropout applied to the LayerNorm's OUTPUT
 // (fpnmt_dropout's arithmetic, key ikey): dy' = keep ? dy / (1 - ip) : 0.
-template <typename T, bool VEC>
+// SYN: x synthesised as in ln_fwd_rows (fpnmt_layernorm_bcast_bwd).
+template <typename T, bool VEC, bool SYN = false>
 __device__ __forceinline__ void ln_bwd_rows(long long blk, long long nblk, long long rows, int d,
                                             const T* __restrict__ x, const T* __restrict__ res,
                                             const float* __restrict__ gamma, const float* __restrict__ mean,
                                             const float* __restrict__ rstd, const T* __restrict__ dy,
                                             T* __restrict__ dx, float* __restrict__ part, float dp,
                                             unsigned long long dkey, T* __restrict__ dz, float ip,
-                                            unsigned long long ikey) {
+                                            unsigned long long ikey, const LnSynth sy = LnSynth{}) {
+#pragma clang fp contract(off)  // as ln_fwd_rows: the one fused step is written out
   const int lane = threadIdx.x & 63;
+  const float ssc = SYN && sy.p > 0.f ? 1.f / (1.f - sy.p) : 1.f;
   const float dsc = dz ? 1.f / (1.f - dp) : 1.f;
   const float isc = ip > 0.f ? 1.f / (1.f - ip) : 1.f;
   const long long wid = (blk * 256LL + threadIdx.x) >> 6;
@@ -983,7 +1024,7 @@ __device__ __forceinline__ void ln_bwd_rows(long long blk, long long nblk, long 
         const int c0 = (lane + 64 * i) * 8;
         bf16x8 xv = {}, rv = {}, dv = {};
         if (c0 < d) {
-          xv = *(const bf16x8*)(x + r * d + c0);
+          if constexpr (!SYN) xv = *(const bf16x8*)(x + r * d + c0);
           if (res) rv = *(const bf16x8*)(res + r * d + c0);
           dv = *(const bf16x8*)(dy + r * d + c0);
         }
@@ -993,7 +1034,9 @@ __device__ __forceinline__ void ln_bwd_rows(long long blk, long long nblk, long 
           xh[k] = 0.f;
           g[k] = 0.f;
           if (c0 < d) {
-            float t = to_f32(xv[e]);
+            float t;
+            if constexpr (SYN) t = ln_synth<T>(sy, ssc, r, r / sy.t, d, c0 + e);
+            else t = to_f32(xv[e]);
             if (res) t = to_f32(from_f32<T>(t + to_f32(rv[e])));
             xh[k] = (t - mu) * rs;
             float dyf = to_f32(dv[e]);
@@ -1015,7 +1058,9 @@ __device__ __forceinline__ void ln_bwd_rows(long long blk, long long nblk, long 
         xh[i] = 0.f;
         g[i] = 0.f;
         if (col < d) {
-          float t = to_f32(x[r * d + col]);
+          float t;
+          if constexpr (SYN) t = ln_synth<T>(sy, ssc, r, r / sy.t, d, col);
+          else t = to_f32(x[r * d + col]);
           if (res) t = to_f32(from_f32<T>(t + to_f32(res[r * d + col])));
           xh[i] = (t - mu) * rs;
           float dyf = to_f32(dy[r * d + col]);
@@ -1039,7 +1084,8 @@ __device__ __forceinline__ void ln_bwd_rows(long long blk, long long nblk, long 
         if (c0 < d) {
           bf16x8 ov;
 #pragma unroll
-          for (int e = 0; e < 8; ++e) ov[e] = from_f32<T>(rs * (g[i * 8 + e] - s1 - xh[i * 8 + e] * s2));
+          for (int e = 0; e < 8; ++e)
+            ov[e] = from_f32<T>(rs * __builtin_fmaf(-xh[i * 8 + e], s2, g[i * 8 + e] - s1));
           *(bf16x8*)(dx + r * d + c0) = ov;
           if (dz) {
 #pragma unroll
@@ -1057,7 +1103,7 @@ __device__ __forceinline__ void ln_bwd_rows(long long blk, long long nblk, long 
       for (int i = 0; i < LN_MAXE; ++i) {
         const int col = lane + 64 * i;
         if (col < d) {
-          const T v = from_f32<T>(rs * (g[i] - s1 - xh[i] * s2));
+          const T v = from_f32<T>(rs * __builtin_fmaf(-xh[i], s2, g[i] - s1));
           dx[r * d + col] = v;
           if (dz) {
             const float t = to_f32(v);
@@ -1102,6 +1148,62 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(long long rows, int d, cons
                                                      T* __restrict__ dz) {
   ln_bwd_rows<T, VEC>(blockIdx.x, gridDim.x, rows, d, x, res, gamma, mean, rstd, dy, dx, part, dp,
                       dz ? drop_key_of(dseed, dseed_dev) : 0ull, dz, 0.f, 0ull);
+}
+
+// ---- the one-key cross-attention sublayer: LN(res + dropout(c[row / t] +
+// cbias)) with the Dense output synthesised per element (LnSynth); the grids,
+// row striding and partial layout are ln_fwd_kernel's / ln_bwd_kernel's
+template <typename T, bool VEC = false>
+__global__ __launch_bounds__(256) void ln_bcast_fwd_kernel(long long rows, int d, float eps, const LnSynth sy,
+                                                           unsigned long long seed,
+                                                           const long long* __restrict__ seed_dev,
+                                                           const T* __restrict__ res,
+                                                           const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, T* __restrict__ y,
+                                                           float* __restrict__ mean_out,
+                                                           float* __restrict__ rstd_out, T* __restrict__ x_out) {
+  LnSynth q = sy;
+  q.key = sy.p > 0.f ? drop_key_of(seed, seed_dev) : 0ull;
+  ln_fwd_rows<T, VEC, true>(blockIdx.x, gridDim.x, rows, d, eps, nullptr, res, gamma, beta, nullptr, 1, y, mean_out,
+                            rstd_out, 0.f, 0ull, q, x_out);
+}
+
+template <typename T, bool VEC = false>
+__global__ __launch_bounds__(256) void ln_bcast_bwd_kernel(long long rows, int d, const LnSynth sy,
+                                                           unsigned long long seed,
+                                                           const long long* __restrict__ seed_dev,
+                                                           const T* __restrict__ res,
+                                                           const float* __restrict__ gamma,
+                                                           const float* __restrict__ mean,
+                                                           const float* __restrict__ rstd,
+                                                           const T* __restrict__ dy, T* __restrict__ dx,
+                                                           float* __restrict__ part, T* __restrict__ dz) {
+  LnSynth q = sy;
+  q.key = sy.p > 0.f ? drop_key_of(seed, seed_dev) : 0ull;
+  ln_bwd_rows<T, VEC, true>(blockIdx.x, gridDim.x, rows, d, nullptr, res, gamma, mean, rstd, dy, dx, part, sy.p, q.key,
+                            dz, 0.f, 0ull, q);
+}
+
+// dc[l][i, col] = sum_j dz_l[i * t + j, col] (fp32, ascending j): thread per
+// column, block (column tile, image i, layer l)
+struct RowsumGroups {
+  const void* dz[FPNMT_MAX_ROWSUM_GROUPS];
+};
+template <typename T>
+__global__ __launch_bounds__(256) void rowsum_groups_kernel(const RowsumGroups G, int b, int t, int d,
+                                                            float* __restrict__ dc, T* __restrict__ dc_lp,
+                                                            T* __restrict__ zero, long long zero_ld,
+                                                            long long zero_so) {
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  const int i = blockIdx.y, l = blockIdx.z;
+  if (col >= d) return;
+  if (zero) zero[l * zero_so + i * zero_ld + col] = from_f32<T>(0.f);
+  const T* src = (const T*)G.dz[l] + (long long)i * t * d + col;
+  float s = 0.f;
+  for (int j = 0; j < t; ++j) s += to_f32(src[(long long)j * d]);
+  const long long o = ((long long)l * b + i) * d + col;
+  dc[o] = s;
+  if (dc_lp) dc_lp[o] = from_f32<T>(s);
 }
 
 // ---- the Encoder's five view LayerNorms (shared gamma / beta / posenc,
@@ -1690,6 +1792,108 @@ int fpnmt_layernorm_bwd_drop(int dtype, long long rows, int d, const void* x, co
   if (!dz) return fail(FPNMT_E_ARG, "layernorm_bwd_drop: null dz");
   return layernorm_bwd_impl(dtype, rows, d, x, res, gamma, mean, rstd, dy, dx, dgamma, dbeta, drop_p, drop_seed,
                             drop_seed_dev, dz, S(stream));
+}
+
+static void log_bcast(const char* op, int dtype, long long rows, int d, int t, float p, bool vec) {
+  if (FILE* f = gemm_log()) {
+    std::fprintf(f, "ln_bcast op=%s dtype=%s rows=%lld d=%d t=%d p=%g vec=%d\n", op, dtype == FPNMT_BF16 ? "bf16" : "f32",
+                 rows, d, t, (double)p, vec ? 1 : 0);
+    std::fflush(f);
+  }
+}
+
+static int ln_bcast_args(long long rows, int d, int t, const float* c, float drop_p) {
+  if (d > 64 * LN_MAXE) return fail(FPNMT_E_UNSUPPORTED, "layernorm: d > 1024");
+  if (!c || t <= 0 || rows % t) return fail(FPNMT_E_ARG, "layernorm_bcast: null c / rows not a multiple of t");
+  if (!(drop_p >= 0.f && drop_p < 1.f)) return fail(FPNMT_E_ARG, "layernorm_bcast: drop_p outside [0, 1)");
+  return 0;
+}
+
+int fpnmt_layernorm_bcast_fwd(int dtype, long long rows, int d, int t, float eps, const float* c, const float* cbias,
+                              float drop_p, unsigned long long drop_seed, const long long* drop_seed_dev,
+                              const void* res, const float* gamma, const float* beta, void* y, float* mean,
+                              float* rstd, void* x_out, fpnmt_stream_t stream) {
+  if (rows <= 0) return 0;
+  if (const int st = ln_bcast_args(rows, d, t, c, drop_p)) return st;
+  if (dtype != FPNMT_BF16 && dtype != FPNMT_F32) return fail(FPNMT_E_ARG, "layernorm_bcast_fwd: bad dtype");
+  const LnSynth sy{c, cbias, t, drop_p, 0ull};
+  const int g = grid_for(rows, 4, 8192);  // fpnmt_layernorm_fwd's grid
+  const bool vec = dtype == FPNMT_BF16 && ln_vec(d, {res, y, x_out});
+  log_bcast("fwd", dtype, rows, d, t, drop_p, vec);
+  if (dtype == FPNMT_BF16) {
+    if (vec)
+      hipLaunchKernelGGL((ln_bcast_fwd_kernel<bf16, true>), dim3(g), dim3(256), 0, S(stream), rows, d, eps, sy,
+                         drop_seed, drop_seed_dev, (const bf16*)res, gamma, beta, (bf16*)y, mean, rstd, (bf16*)x_out);
+    else
+      hipLaunchKernelGGL((ln_bcast_fwd_kernel<bf16>), dim3(g), dim3(256), 0, S(stream), rows, d, eps, sy, drop_seed,
+                         drop_seed_dev, (const bf16*)res, gamma, beta, (bf16*)y, mean, rstd, (bf16*)x_out);
+  } else {
+    hipLaunchKernelGGL((ln_bcast_fwd_kernel<float>), dim3(g), dim3(256), 0, S(stream), rows, d, eps, sy, drop_seed,
+                       drop_seed_dev, (const float*)res, gamma, beta, (float*)y, mean, rstd, (float*)x_out);
+  }
+  return check_launch("layernorm_bcast_fwd");
+}
+
+int fpnmt_layernorm_bcast_bwd(int dtype, long long rows, int d, int t, const float* c, const float* cbias,
+                              float drop_p, unsigned long long drop_seed, const long long* drop_seed_dev,
+                              const void* res, const float* gamma, const float* mean, const float* rstd,
+                              const void* dy, void* dx, float* dgamma, float* dbeta, void* dz,
+                              fpnmt_stream_t stream) {
+  if (rows <= 0) return 0;
+  if (const int st = ln_bcast_args(rows, d, t, c, drop_p)) return st;
+  if (dtype != FPNMT_BF16 && dtype != FPNMT_F32) return fail(FPNMT_E_ARG, "layernorm_bcast_bwd: bad dtype");
+  if (!dz && drop_p > 0.f) return fail(FPNMT_E_ARG, "layernorm_bcast_bwd: null dz with drop_p > 0");
+  if (drop_p <= 0.f) dz = nullptr;  // dz == dx
+  hipStream_t s = S(stream);
+  const LnSynth sy{c, cbias, t, drop_p, 0ull};
+  const int g = grid_for(rows, 4, 1024);  // fpnmt_layernorm_bwd's grid and partial rows
+  float* part = nullptr;
+  if (dgamma || dbeta) {
+    part = partial_f32((long long)g * 2 * d);
+    if (!part) return fail(FPNMT_E_ARG, "layernorm_bcast_bwd: dgamma / dbeta need the fpnmt workspace");
+  }
+  const bool vec = dtype == FPNMT_BF16 && ln_vec(d, {res, dy, dx, dz});
+  log_bcast("bwd", dtype, rows, d, t, drop_p, vec);
+  if (dtype == FPNMT_BF16) {
+    if (vec)
+      hipLaunchKernelGGL((ln_bcast_bwd_kernel<bf16, true>), dim3(g), dim3(256), 0, s, rows, d, sy, drop_seed,
+                         drop_seed_dev, (const bf16*)res, gamma, mean, rstd, (const bf16*)dy, (bf16*)dx, part,
+                         (bf16*)dz);
+    else
+      hipLaunchKernelGGL((ln_bcast_bwd_kernel<bf16>), dim3(g), dim3(256), 0, s, rows, d, sy, drop_seed, drop_seed_dev,
+                         (const bf16*)res, gamma, mean, rstd, (const bf16*)dy, (bf16*)dx, part, (bf16*)dz);
+  } else {
+    hipLaunchKernelGGL((ln_bcast_bwd_kernel<float>), dim3(g), dim3(256), 0, s, rows, d, sy, drop_seed, drop_seed_dev,
+                       (const float*)res, gamma, mean, rstd, (const float*)dy, (float*)dx, part, (float*)dz);
+  }
+  if (part) colsum_launch(g, 2 * d, part, dgamma, s, d, dbeta);
+  return check_launch("layernorm_bcast_bwd");
+}
+
+int fpnmt_rowsum_groups(int dtype, int n, int b, int t, int d, const void* const* dz, float* dc, void* dc_lp,
+                        void* zero, long long zero_ld, long long zero_so, fpnmt_stream_t stream) {
+  if (n < 0 || n > FPNMT_MAX_ROWSUM_GROUPS) return fail(FPNMT_E_ARG, "rowsum_groups: 0 <= n <= FPNMT_MAX_ROWSUM_GROUPS");
+  if (n == 0 || b <= 0 || d <= 0) return 0;
+  if (t < 0 || b > 65535 || !dz || !dc) return fail(FPNMT_E_ARG, "rowsum_groups: bad shape / null pointer");
+  if (dtype != FPNMT_BF16 && dtype != FPNMT_F32) return fail(FPNMT_E_ARG, "rowsum_groups: bad dtype");
+  if (zero && (zero_ld < d || zero_so < 0)) return fail(FPNMT_E_ARG, "rowsum_groups: zero_ld < d / zero_so < 0");
+  RowsumGroups G{};
+  for (int l = 0; l < n; ++l) {
+    if (!dz[l] && t > 0) return fail(FPNMT_E_ARG, "rowsum_groups: null dz");
+    G.dz[l] = dz[l];
+  }
+  if (FILE* f = gemm_log()) {
+    std::fprintf(f, "rowsum_groups dtype=%s n=%d b=%d t=%d d=%d\n", dtype == FPNMT_BF16 ? "bf16" : "f32", n, b, t, d);
+    std::fflush(f);
+  }
+  const dim3 grid(cdiv(d, 256), b, n);
+  if (dtype == FPNMT_BF16)
+    hipLaunchKernelGGL((rowsum_groups_kernel<bf16>), grid, dim3(256), 0, S(stream), G, b, t, d, dc, (bf16*)dc_lp,
+                       (bf16*)zero, zero_ld, zero_so);
+  else
+    hipLaunchKernelGGL((rowsum_groups_kernel<float>), grid, dim3(256), 0, S(stream), G, b, t, d, dc, (float*)dc_lp,
+                       (float*)zero, zero_ld, zero_so);
+  return check_launch("rowsum_groups");
 }
 
 static bool ln_views_vec(int n, int d, const fpnmt_ln_view* v, bool bwd) {

@@ -120,6 +120,19 @@ class _Config:
     # join costs more than the ~80 us it hides; bitwise equal either way
     # (test_zero_grad_overlap_bitwise_equal)
     zero_grad_overlap_grid = 0
+    # the decoder's cross-attention over ONE unmasked encoder key (every 224^2
+    # workload: the baseline view is one token per image): the softmax weight
+    # is exactly 1, so per layer the query projection, the attention and the
+    # (B*T)-row output Dense are replaced by one batched (layers, B)-row GEMM
+    # ahead of the layers (ops.CrossOneKeyFn) and a LayerNorm that synthesises
+    # the Dense output per element (ops.LayerNormBcastFn). Taken only with
+    # enc_output.shape[1] == 1, no padding mask and fuse_projections
+    cross_one_key = True
+    # ... and that LayerNorm's forward also stores the synthesised Dense output
+    # (rows x d, 1 MB per layer at C2), so its backward is the general path's
+    # launch reading it (fpnmt_layernorm_bwd_drop) instead of a launch that
+    # recomputes the dropout hash per element (fpnmt_layernorm_bcast_bwd)
+    cross_one_key_store_x = True
 
 
 config = _Config()

@@ -60,6 +60,7 @@ def assert_in_tree():
                            "unset them for benchmarks, smoke and tests")
 
 F32, BF16 = 0, 1
+MAX_ROWSUM_GROUPS = 16  # FPNMT_MAX_ROWSUM_GROUPS
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_RELU6 = 0, 1, 2, 3
 
 
@@ -193,6 +194,9 @@ SIGNATURES = {
     "fpnmt_layernorm_fwd": [I, LL, I, F, P, P, P, P, P, I, P, P, P, P],
     "fpnmt_layernorm_bwd": [I, LL, I, P, P, P, P, P, P, P, P, P, P],
     "fpnmt_layernorm_bwd_drop": [I, LL, I, P, P, P, P, P, P, P, P, P, F, ULL, P, P, P],
+    "fpnmt_layernorm_bcast_fwd": [I, LL, I, I, F, P, P, F, ULL, P, P, P, P, P, P, P, P, P],
+    "fpnmt_layernorm_bcast_bwd": [I, LL, I, I, P, P, F, ULL, P, P, P, P, P, P, P, P, P, P, P],
+    "fpnmt_rowsum_groups": [I, I, I, I, I, C.POINTER(C.c_void_p), P, P, P, LL, LL, P],
     "fpnmt_decoder_targets": [I, I, P, I, LL, P, P, P, P],
     "fpnmt_layernorm_views_fwd": [I, I, I, F, C.POINTER(LnView), P, P, P, F, P, P],
     "fpnmt_layernorm_views_bwd": [I, I, I, C.POINTER(LnView), P, F, P, P, P, P],

@@ -337,10 +337,13 @@ class DenseGroup:
     The members keep their own parameters (state dicts unchanged); their
     forward compute copies become slices of one stacked (n*out, in) operand.
     ``arena_order`` lists the members' kernels then biases so a ParamArena
-    built in that order holds each as one contiguous block."""
+    built in that order holds each as one contiguous block; reorder=False
+    leaves the members where they are in the arena (only the compute copies
+    are stacked; grad_views() then finds no contiguous block)."""
 
-    def __init__(self, layers):
+    def __init__(self, layers, reorder=True):
         self.layers = list(layers)
+        self.reorder = reorder
         fin, fout = self.layers[0].kernel.shape
         for m in self.layers:
             if tuple(m.kernel.shape) != (fin, fout) or m.activation not in (None, "linear") or m.out_f32 \
@@ -427,7 +430,7 @@ def group_param_order(model, named):
     seen = set()
     for m in model.modules():
         g = m.__dict__.get("_group")
-        if g is not None and id(g[0]) not in seen:
+        if g is not None and id(g[0]) not in seen and g[0].reorder:
             seen.add(id(g[0]))
             groups.append(g[0])
     name_of = {id(p): n for n, p in named}

@@ -1834,6 +1834,223 @@ class LayerNormViewsFn(torch.autograd.Function):
         return (None, None, None, *dxs)
 
 
+# --------------------------------------------- one-key cross-attention
+class _OneKeyBox:
+    """Shared by a CrossOneKeyFn node and the LayerNormBcastFn nodes that read
+    its outputs: each layer's LayerNorm backward parks its dz here, and the
+    CrossOneKeyFn backward (which runs after all of them: every one consumes
+    one of its outputs) reduces them in one launch."""
+    __slots__ = ("dzs",)
+
+    def __init__(self, n):
+        self.dzs = [None] * n
+
+
+def _uniform_stride(ts):
+    """Element offset between consecutive tensors of ts when they sit at a
+    constant stride in one storage (0 for a single tensor), else None."""
+    es = ts[0].element_size()
+    base = ts[0].data_ptr()
+    if len(ts) == 1:
+        return 0
+    step = ts[1].data_ptr() - base
+    if step <= 0 or step % es:
+        return None
+    for i, t in enumerate(ts):
+        if t.data_ptr() != base + i * step or t.untyped_storage().data_ptr() != ts[0].untyped_storage().data_ptr():
+            return None
+    return step // es
+
+
+class CrossOneKeyFn(torch.autograd.Function):
+    """Every decoder layer's cross-attention over ONE unmasked encoder key
+    (DecoderLayer.mha2 at a 1-token encoder output, transformer.py:226-229):
+    the softmax weight is exactly 1, the attention output is v_l[b] for every
+    query row, and the output Dense gives the same row c_l[b] = v_l[b] W_o,l
+    (+ b_o,l, added where the row is used) for all T positions. ONE batched
+    GEMM (batch = layers, M = B) produces all c_l in fp32; q and k are not
+    needed. Inputs: the K and V slices of the grouped projection ((B, 1, d)
+    each; the K slices only receive their zero gradient). Backward (after all
+    layers' LayerNormBcastFn backwards parked their dz): one row-sum launch
+    dc_l[b] = sum_t dz_l[b, t] (also zeroing dK in the group's gradient
+    buffer), one batched dc -> dv GEMM into that buffer, the output kernels'
+    gradients as deferred Dense jobs with K = B rows, the output biases'
+    as deferred column sums of the fp32 dc."""
+
+    @staticmethod
+    def forward(ctx, o_group, box, *kv):
+        n, fin, fout = o_group.n, o_group.fin, o_group.fout
+        if len(kv) != 2 * n:
+            raise ValueError("CrossOneKeyFn: one (k, v) per layer")
+        ks, vs = kv[:n], kv[n:]
+        B = vs[0].shape[0]
+        if any(tuple(t.shape) != (B, 1, fin) for t in kv) or fin != fout:
+            raise ValueError("CrossOneKeyFn: (B, 1, d) keys / values and a square output Dense")
+        slots = [_slot_of(t) for t in kv]
+        slots = [sl if sl is not None and sl[0].claim(sl[1]) else None for sl in slots]
+        cdt = vs[0].dtype
+        dt = dtype_code(cdt)
+        vs = [_rows_view(v) for v in vs]
+        a_so = _uniform_stride(vs)
+        if a_so is None or len({_row_ld(v) for v in vs}) != 1:
+            vs = list(torch.stack([v.reshape(B, fin) for v in vs]).unbind(0))
+            vs = [v.view(B, 1, fin) for v in vs]
+            a_so = B * fin
+        lda = _row_ld(vs[0])
+        stack, _ = o_group.stacked(cdt)
+        c = _empty((n, B, fout), torch.float32, vs[0].device)
+        g = _gemm_desc(B, fout, fin, dt, lda, fin, fout, c_f32=1 if cdt != torch.float32 else 0)
+        g.batch = n
+        g.a_so, g.b_so, g.c_so = a_so, fout * fin, B * fout
+        call("fpnmt_gemm", g, ptr(vs[0]), ptr(stack), ptr(c), None, None, None, stream_ptr())
+        ctx.o_group, ctx.box, ctx.slots, ctx.B = o_group, box, slots, B
+        ctx.a_so, ctx.lda = a_so, lda
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*vs)
+        return tuple(c[i] for i in range(n))
+
+    @staticmethod
+    def backward(ctx, *_gc):
+        vs = ctx.saved_tensors
+        group, box, B = ctx.o_group, ctx.box, ctx.B
+        n, fin, fout = group.n, group.fin, group.fout
+        dzs, box.dzs = box.dzs, [None] * n
+        if all(z is None for z in dzs):
+            return (None,) * (2 + 2 * n)
+        if any(z is None for z in dzs):
+            raise RuntimeError("CrossOneKeyFn: some decoder layers were not back-propagated")
+        cdt = vs[0].dtype
+        dt = dtype_code(cdt)
+        dev = vs[0].device
+        s = stream_ptr()
+        T = dzs[0].numel() // (B * fout)
+        # gradient destinations: the grouped projection's buffer when every
+        # slice came from one (dk zeroed and dv written in place), else dense
+        slots = ctx.slots
+        same = all(sl is not None and sl[0] is slots[0][0] for sl in slots)
+        if same:
+            slot = slots[0][0]
+            grads = [slot.view(sl[1], (B, 1, fin)) for sl in slots]
+        else:
+            buf = _empty((B, 2 * n * fin), cdt, dev)
+            grads = [buf[:, i * fin:(i + 1) * fin].view(B, 1, fin) for i in range(2 * n)]
+        dks, dvs = grads[:n], grads[n:]
+        k_so, v_so = _uniform_stride(dks), _uniform_stride(dvs)
+        if k_so is None or v_so is None or n > L.MAX_ROWSUM_GROUPS:
+            raise RuntimeError("CrossOneKeyFn: the layers' key / value gradients must sit at a constant stride")
+        dc = _empty((n, B, fout), torch.float32, dev)
+        dcl = dc if cdt == torch.float32 else _empty((n, B, fout), cdt, dev)
+        import ctypes
+        tab = (ctypes.c_void_p * n)(*[z.data_ptr() for z in dzs])
+        call("fpnmt_rowsum_groups", dt, n, B, T, fout, tab, ptr(dc), ptr(dcl) if dcl is not dc else None,
+             ptr(dks[0]), _row_ld(dks[0]), k_so, s)
+        # dv_l = dc_l W_o,l^T: one batched bwd-data launch
+        _, flip = group.stacked(cdt)
+        g = _gemm_desc(B, fin, fout, dt, fout, n * fout, _row_ld(dvs[0]))
+        g.batch = n
+        g.a_so, g.b_so, g.c_so = B * fout, fout, v_so
+        call("fpnmt_gemm", g, ptr(dcl), ptr(flip), ptr(dvs[0]), None, None, None, s)
+        # output biases: column sums of the fp32 dc_l over the B images
+        kg, bg = group.grad_views()
+        for i, m in enumerate(group.layers):
+            if m.bias.requires_grad:
+                bias_grad(L.F32, B, fout, dc[i], _grad_of(m.bias).data_ptr(), s)
+        # output kernels: dW_o,l += v_l^T dc_l (K = B rows)
+        if kg is not None:
+            g = _gemm_desc(fin, fout, B, dt, ctx.lda, fout, fout, a_trans=1, b_trans=1, accumulate=2, c_f32=1)
+            g.batch = n
+            g.a_so, g.b_so, g.c_so = ctx.a_so, B * fout, fin * fout
+            _wgrad(lambda: call("fpnmt_gemm_wgrad", g, ptr(vs[0]), ptr(dcl), ptr(kg), stream_ptr()), *vs, dcl)
+        else:
+            for i, m in enumerate(group.layers):
+                g = _gemm_desc(fin, fout, B, dt, ctx.lda, fout, fout, a_trans=1, b_trans=1, accumulate=2, c_f32=1)
+                gk = _grad_of(m.kernel)
+                _wgrad(lambda g=g, i=i, gk=gk: call("fpnmt_gemm_wgrad", g, ptr(vs[i]), dcl[i].data_ptr(), ptr(gk),
+                                                    stream_ptr()), vs[i], dcl)
+        return (None, None, *dks, *dvs)
+
+
+class LayerNormBcastFn(torch.autograd.Function):
+    """LN(res + Dropout(c[b] + bias)) for the T rows of every image b (the
+    one-key cross-attention sublayer's `out2 = layernorm2(attn2 + out1)`,
+    transformer.py:230-233): the (B*T, d) Dense output is never stored, the
+    LayerNorm synthesises it per element with the dropout mask, seed and
+    rounding of the Dense GEMM epilogue (fpnmt_layernorm_bcast_fwd). With
+    config.cross_one_key_store_x the forward also stores that x and the
+    backward is the general path's launch on it (fpnmt_layernorm_bwd_drop, or
+    fpnmt_layernorm_bwd + the separate dropout pass without
+    config.fuse_drop_ln); otherwise fpnmt_layernorm_bcast_bwd recomputes x.
+    The backward parks dz (the Dense's masked gradient) in the box for
+    CrossOneKeyFn and returns dx, the whole gradient of res."""
+
+    @staticmethod
+    def forward(ctx, res, c, layer, dense, drop_p, box, idx):
+        ctx.rsink_res = _sink_for_res(res)
+        res = res.contiguous()
+        d = res.shape[-1]
+        t = res.shape[-2]
+        rows = res.numel() // d if d else 0
+        if c.dtype != torch.float32 or not c.is_contiguous() or c.numel() * t != res.numel():
+            raise ValueError("LayerNormBcastFn: c must be a contiguous fp32 (B, d) for res (B, T, d)")
+        seed, st = 0, None
+        if drop_p > 0.0:
+            seed, st = runtime.next_seed(), runtime.seed_tensor
+        y = torch.empty_like(res)
+        mean = _empty((max(rows, 1),), torch.float32, res.device)
+        rstd = _empty((max(rows, 1),), torch.float32, res.device)
+        import fpnmt
+        x = torch.empty_like(res) if fpnmt.config.cross_one_key_store_x and any(ctx.needs_input_grad) else None
+        call("fpnmt_layernorm_bcast_fwd", dtype_code(res.dtype), rows, d, t, layer.epsilon, ptr(c), ptr(dense.bias),
+             float(drop_p), seed, ptr(st), ptr(res), ptr(layer.gamma), ptr(layer.beta), ptr(y), ptr(mean), ptr(rstd),
+             ptr(x), stream_ptr())
+        ctx.layer, ctx.dense, ctx.drop, ctx.box, ctx.idx = layer, dense, (float(drop_p), seed, st), box, idx
+        ctx.fuse_drop = bool(fpnmt.config.fuse_drop_ln)
+        ctx.save_for_backward(res, c, mean, rstd, x)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        res, c, mean, rstd, x = ctx.saved_tensors
+        layer = ctx.layer
+        d, t = res.shape[-1], res.shape[-2]
+        rows = res.numel() // d if d else 0
+        p, seed, st = ctx.drop
+        dt = dtype_code(res.dtype)
+        dx = torch.empty_like(res)
+        dz = torch.empty_like(res) if p > 0.0 else None
+        dy = dy.contiguous()
+        dg, db = ptr(_grad_of(layer.gamma)), ptr(_grad_of(layer.beta))
+        if x is None:  # recompute the synthesised x
+            call("fpnmt_layernorm_bcast_bwd", dt, rows, d, t, ptr(c), ptr(ctx.dense.bias), p, seed, ptr(st), ptr(res),
+                 ptr(layer.gamma), ptr(mean), ptr(rstd), ptr(dy), ptr(dx), dg, db, ptr(dz), stream_ptr())
+        elif dz is not None and ctx.fuse_drop:
+            call("fpnmt_layernorm_bwd_drop", dt, rows, d, ptr(x), ptr(res), ptr(layer.gamma), ptr(mean), ptr(rstd),
+                 ptr(dy), ptr(dx), dg, db, p, seed, ptr(st), ptr(dz), stream_ptr())
+        else:
+            call("fpnmt_layernorm_bwd", dt, rows, d, ptr(x), ptr(res), ptr(layer.gamma), ptr(mean), ptr(rstd), ptr(dy),
+                 ptr(dx), dg, db, stream_ptr())
+            if dz is not None:  # the Dense's dropout backward as its own pass (no bias sums: they come from dc)
+                act_bwd(dt, rows, d, L.ACT_NONE, 0.0, dx, None, dz, None, stream_ptr(), drop=ctx.drop)
+        ctx.box.dzs[ctx.idx] = dz if dz is not None else dx
+        return _sink_put(ctx.rsink_res, dx), None, None, None, None, None, None
+
+
+_ONES_CACHE = {}
+
+
+def cached_ones(shape, dtype, device):
+    """A constant tensor of ones, filled once per (shape, dtype, device): the
+    one-key attention weights the decoder reports. Built outside a stream
+    capture only (a capture would record the fill and own the memory)."""
+    key = (tuple(shape), dtype, str(device))
+    t = _ONES_CACHE.get(key)
+    if t is None:
+        t = torch.ones(shape, dtype=dtype, device=device)
+        if not (t.is_cuda and torch.cuda.is_current_stream_capturing()):
+            _ONES_CACHE[key] = t
+    return t
+
+
 # --------------------------------------------------------------- embedding
 class EmbedPosencFn(torch.autograd.Function):
     @staticmethod

@@ -177,9 +177,11 @@ class DecoderLayer(nn.Module):
         self.rate = rate
         self.qkv_group = DenseGroup([self.mha1.wq, self.mha1.wk, self.mha1.wv])
 
-    def forward(self, x, enc_output, training, look_ahead_mask, padding_mask, kv2=None):
+    def forward(self, x, enc_output, training, look_ahead_mask, padding_mask, kv2=None, one_key=None):
         """kv2: this layer's cross-attention (k, v) from the Decoder's grouped
-        K/V GEMM over enc_output, or None."""
+        K/V GEMM over enc_output, or None. one_key: (c, box, index) from the
+        Decoder's ops.CrossOneKeyFn when enc_output is one unmasked key: the
+        cross-attention sublayer is then a function of c = v W_o alone."""
         fused = fpnmt.config.fuse_projections
         drop = self.rate if training else 0.0
         if fused:
@@ -188,6 +190,15 @@ class DecoderLayer(nn.Module):
         else:
             attn1, attn_weights_block1 = self.mha1(x, x, x, look_ahead_mask, dropout=drop)
         out1 = self.layernorm1(attn1, residual=x)
+        if one_key is not None:
+            # softmax over one key is exactly 1: out2 = LN2(out1 + dropout(c[b] + b_o)), no q / attention / Dense
+            c, box, idx = one_key
+            out2 = ops.LayerNormBcastFn.apply(out1, c, self.layernorm2, self.mha2.dense, drop, box, idx)
+            attn_weights_block2 = ops.cached_ones((out1.shape[0], self.mha2.num_heads, out1.shape[1], 1),
+                                                  out1.dtype, out1.device)
+            ffn_output = self.ffn2(self.ffn1(out2), dropout=drop)
+            out3 = self.layernorm3(ffn_output, residual=out2)
+            return out3, attn_weights_block1, attn_weights_block2
         if fused and kv2 is not None:
             attn2, attn_weights_block2 = self.mha2.attend(self.mha2.wq(out1), kv2[0], kv2[1], padding_mask,
                                                           dropout=drop)
@@ -274,6 +285,18 @@ class Decoder(nn.Module):
         # enc_output feeds every layer's cross-attention K/V: one GEMM
         self.cross_kv_group = DenseGroup([w for l in self.dec_layers for w in (l.mha2.wk, l.mha2.wv)]) \
             if num_layers > 0 else None
+        # the cross-attention output Dense layers: at one encoder key they run
+        # as one batched GEMM for all layers (ops.CrossOneKeyFn); only their
+        # compute copies are stacked, the parameters keep their arena places
+        self.cross_o_group = DenseGroup([l.mha2.dense for l in self.dec_layers], reorder=False) \
+            if num_layers > 0 else None
+
+    def one_key(self, enc_output, padding_mask, kv):
+        """The one-key fast path applies: a host-side, shape-level decision
+        (safe under graph capture)."""
+        return (fpnmt.config.cross_one_key and kv is not None and enc_output.dim() == 3
+                and enc_output.shape[1] == 1 and padding_mask is None
+                and self.num_layers <= fpnmt._lib.MAX_ROWSUM_GROUPS)
 
     def forward(self, x, enc_output, training, look_ahead_mask, padding_mask):
         seq_len = x.shape[1]
@@ -286,9 +309,14 @@ class Decoder(nn.Module):
             x = self.embedding(x, self.pos_encoding, enc_output.dtype)
             x = ops.dropout(x, self.rate, training)
         kv = self.cross_kv_group(enc_output) if (fpnmt.config.fuse_projections and self.cross_kv_group) else None
+        cs = box = None
+        if self.one_key(enc_output, padding_mask, kv):
+            box = ops._OneKeyBox(self.num_layers)
+            cs = ops.CrossOneKeyFn.apply(self.cross_o_group, box, *kv[0::2], *kv[1::2])
         for i in range(self.num_layers):
             kv2 = (kv[2 * i], kv[2 * i + 1]) if kv is not None else None
-            x, block1, block2 = self.dec_layers[i](x, enc_output, training, look_ahead_mask, padding_mask, kv2=kv2)
+            x, block1, block2 = self.dec_layers[i](x, enc_output, training, look_ahead_mask, padding_mask, kv2=kv2,
+                                                   one_key=(cs[i], box, i) if cs is not None else None)
             attention_weights["decoder_layer{}_block1".format(i + 1)] = block1
             attention_weights["decoder_layer{}_block2".format(i + 1)] = block2
         return x, attention_weights

@@ -524,6 +524,45 @@ int fpnmt_layernorm_bwd_drop(int dtype, long long rows, int d, const void* x, co
                              unsigned long long drop_seed, const long long* drop_seed_dev, void* dz,
                              fpnmt_stream_t stream);
 
+/* ---- one-key cross-attention sublayer (DecoderLayer, transformer.py:226-233)
+ * With ONE unmasked encoder key the softmax weight is exactly 1: the
+ * attention output is v[b] for each of an image's t query rows, and the
+ * sublayer's Dense output row is c[b] + cbias, c[b] = v[b] W_o (fp32, the
+ * unrounded GEMM accumulator). `out2 = LN(out1 + dropout(dense))` then needs
+ * no (rows, d) Dense output in memory: the LayerNorm synthesises its x operand
+ *   x[r, col] = T(keep(r*d + col) ? (c[r / t, col] + cbias[col]) / (1 - p) : 0)
+ * with keep / key of fpnmt_gemm's dropout epilogue (the value that GEMM
+ * would have stored from the same accumulator), rows = b*t, c (rows / t, d)
+ * fp32, cbias optional. Row striding, the T(x + res) rounding, mean / rstd and
+ * y are fpnmt_layernorm_fwd's on the materialised x, bit for bit. x_out
+ * (optional, rows x d): the synthesised x is also stored, for a backward that
+ * reads it (fpnmt_layernorm_bwd / _bwd_drop) instead of recomputing it.
+ * bcast_bwd: fpnmt_layernorm_bwd_drop on that x: dx (now the only gradient of
+ * res), dgamma / dbeta partials in the same layout and order, and
+ * dz = keep ? dx / (1 - p) : 0 (dz may be NULL when drop_p == 0: dz == dx).  */
+int fpnmt_layernorm_bcast_fwd(int dtype, long long rows, int d, int t, float eps, const float* c,
+                              const float* cbias, float drop_p, unsigned long long drop_seed,
+                              const long long* drop_seed_dev, const void* res, const float* gamma,
+                              const float* beta, void* y, float* mean, float* rstd, void* x_out,
+                              fpnmt_stream_t stream);
+int fpnmt_layernorm_bcast_bwd(int dtype, long long rows, int d, int t, const float* c, const float* cbias,
+                              float drop_p, unsigned long long drop_seed, const long long* drop_seed_dev,
+                              const void* res, const float* gamma, const float* mean, const float* rstd,
+                              const void* dy, void* dx, float* dgamma, float* dbeta, void* dz,
+                              fpnmt_stream_t stream);
+/* The gradients of c for n layers in one launch: dc[l][i, col] = sum over the
+ * t rows of image i of dz[l][i*t + j, col], fp32, ascending j, no atomics
+ * (deterministic). dz: n host pointers to (b*t, d) tensors of the dtype
+ * (n <= FPNMT_MAX_ROWSUM_GROUPS); dc (n, b, d) fp32; dc_lp (optional): the
+ * same sums rounded to the dtype (a GEMM operand). zero (optional): the launch
+ * also stores zeros of the dtype to n (b, d) blocks, element (l, i, col) at
+ * zero + l*zero_so + i*zero_ld + col (elements): the gradient of the key
+ * projections, which one-key attention does not depend on, written into the
+ * grouped projection's gradient buffer beside dv with no fill launch.       */
+#define FPNMT_MAX_ROWSUM_GROUPS 16
+int fpnmt_rowsum_groups(int dtype, int n, int b, int t, int d, const void* const* dz, float* dc, void* dc_lp,
+                        void* zero, long long zero_ld, long long zero_so, fpnmt_stream_t stream);
+
 /* ---- decoder embedding + positional encoding ---------------------------
  * y[b,t,:] = E[tok[b,t],:] + pe[t,:]   (no sqrt(d) scale, transformer.py:326-329)
  * bwd: dE[tok] += dy rows, each id's rows summed in position order (no
