@@ -28,6 +28,8 @@ FILE* gemm_log() {
   }();
   return f;
 }
+static int g_wide_cfg = 0;
+int forced_wide_cfg() { return g_wide_cfg; }
 void log_attn(const char* op, const char* kernel, int dtype, int b, int h, int lq, int lk, int d, int n_views) {
   if (FILE* f = gemm_log()) {
     std::fprintf(f, "attn op=%s kernel=%s dtype=%s b=%d h=%d lq=%d lk=%d d=%d", op, kernel,
@@ -228,6 +230,14 @@ int fpnmt_set_workspace(void* ws, long long bytes) {
   g_split_ws.part_floats = (bytes - cnt_bytes) / 4;
   return 0;
 }
+
+int fpnmt_set_wide_cfg(int cfg) {
+  if (cfg != 0 && cfg != 6 && cfg != 10)
+    return fail(FPNMT_E_ARG, "set_wide_cfg: cfg must be 0 (automatic), 6 or 10, got " + std::to_string(cfg));
+  g_wide_cfg = cfg;
+  return 0;
+}
+int fpnmt_get_wide_cfg(void) { return g_wide_cfg; }
 
 static int gemm_impl_api(const fpnmt_gemm_desc* d, const void* A, const void* B, void* C, const float* col_scale,
                          const float* bias, const void* R, int r_mask, float mask_alpha, fpnmt_stream_t stream);

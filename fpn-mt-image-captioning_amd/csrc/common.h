@@ -26,6 +26,8 @@ void log_attn(const char* op, const char* kernel, int dtype, int b, int h, int l
 inline void log_attn(const char* op, const char* kernel, const fpnmt_attn_desc* d, int n_views = -1) {
   log_attn(op, kernel, d->dtype, d->b, d->h, d->lq, d->lk, d->d, n_views);
 }
+// fpnmt_set_wide_cfg (api.hip): the wide conv classes' forced tile form, 0 = automatic (gemm_dispatch.h)
+int forced_wide_cfg();
 // Zero fills as kernels (api.hip). hipMemsetAsync / hipMemset2DAsync inside a
 // captured hipGraph were measured NOT to re-zero on replay (tools/probes/
 // conv_noise.py: the strided 1x1 bwd-data accumulated onto stale memory), so

@@ -102,8 +102,8 @@ int launch_wg_jobs(const DefConvWg* jobs_in, int n, hipStream_t s) {
         ++i;
       }
       if (FILE* f = gemm_log()) {
-        std::fprintf(f, "bf16 a=%d b=%d c=0 M=0 N=0 K=0 batch=1 acc=2 split=0 cfg=112 jobs=%d blocks=%lld tile=%dx%d\n",
-                     A_IM2COL_T, B_KN, J.n, blocks, tile[cls][0], tile[cls][1]);
+        std::fprintf(f, "bf16 a=%d b=%d c=0 M=0 N=0 K=0 batch=1 acc=2 split=0 cfg=%d jobs=%d blocks=%lld tile=%dx%d\n",
+                     A_IM2COL_T, B_KN, ROUTE_WG_JOBS, J.n, blocks, tile[cls][0], tile[cls][1]);
         std::fflush(f);
       }
       int st = 0;

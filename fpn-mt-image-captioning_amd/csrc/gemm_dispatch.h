@@ -6,8 +6,8 @@
 // kernel is occupancy/latency bound at these sizes, so 64x64 tiles win unless
 // 128x128 still gives >= 1.5 blocks per CU; BK = 64 pays for deep K (>= 1024).
 #pragma once
+#include <algorithm>
 #include <cstdio>
-#include <cstdlib>
 #include "gemm_impl.h"
 #include "gemm_pipe.h"
 #include "gemm_skinny.h"
@@ -26,24 +26,32 @@ static int cu_count_dispatch() {
 }
 
 enum { CFG_128_128_64 = 0, CFG_64_64_32, CFG_64_64_64, CFG_128_128_32, CFG_32_32_32, CFG_SMALL };
-struct TileCfg {
-  int bm, bn, bk;
-};
+struct TileCfg { int bm, bn, bk; };
 static const TileCfg kCfg[] = {{128, 128, 64}, {64, 64, 32}, {64, 64, 64}, {128, 128, 32}, {32, 32, 32}, {32, 64, 16}};
+
+// Tiles of `step` along M (along_k: along K) in total. A launch grouped along
+// that dimension sums its groups, which own consecutive tile ranges (k-grouped:
+// reductions end to end); with `starts`, starts[g].start = the group's first.
+static long long group_tiles(const GemmParams& p, bool along_k, int step, GemmGroup* starts = nullptr) {
+  if (p.ngroups <= 0 || (p.group_k != 0) != along_k) return cdiv(along_k ? p.K : p.M, step);
+  long long t = 0;
+  for (int g = 0; g < p.ngroups; ++g) {
+    if (starts) starts[g].start = (int)t;
+    t += cdiv(along_k ? p.groups[g].K : p.groups[g].M, step);
+  }
+  return t;
+}
+static long long m_tiles(const GemmParams& p, int ms) { return group_tiles(p, false, ms); }
+static long long k_tiles(const GemmParams& p, int bk) { return group_tiles(p, true, bk); }
+// the launch's tile grid at M step ms and tile width bn (and the m-groups' starts)
+static void set_tile_grid(GemmParams& p, int ms, int bn) {
+  p.tiles_m = (int)group_tiles(p, false, ms, p.groups);
+  p.tiles_n = cdiv(p.N, bn);
+}
 
 template <typename T, int BM, int BN, int WM, int WN, int AM, int BMODE, int BK>
 static int launch_one(GemmParams& p, int batch, bool vec, hipStream_t s) {
-  if (p.ngroups > 0 && !p.group_k) {  // m-grouped: groups own consecutive m-tile ranges
-    int t = 0;
-    for (int g = 0; g < p.ngroups; ++g) {
-      p.groups[g].start = t;
-      t += cdiv(p.groups[g].M, BM);
-    }
-    p.tiles_m = t;
-  } else {
-    p.tiles_m = cdiv(p.M, BM);
-  }
-  p.tiles_n = cdiv(p.N, BN);
+  set_tile_grid(p, BM, BN);
   dim3 grid(p.tiles_m * p.tiles_n, p.split_k, batch);
   dim3 block(64 * WM * WN);
   if (vec)
@@ -118,21 +126,24 @@ static int launch_small(GemmParams& p, int batch, hipStream_t s) {
   return check_launch("gemm_small_kernel");
 }
 
-// bf16 gets the BK=64 variants; f32 (parity mode) keeps BK=16 everywhere.
-template <typename T> constexpr int bk_of(int bk) { return std::is_same<T, float>::value ? 16 : bk; }
+// gemm_kernel's BKT argument for (T, A operand mode, cfg): bf16 gets the
+// BK = 64 variants where they are instantiated; 0 = the type's default K-tile
+// (bf16 32; f32, parity mode, keeps 16 everywhere). The one rule for the
+// instantiation (launch_cfg) and the split policy's K-tile depth (staged_bk).
+template <typename T>
+constexpr int staged_bkt(int am, int cfg) {
+  if (std::is_same<T, float>::value) return 0;
+  if (cfg == CFG_128_128_64 && (am == A_IM2COL || am == A_ROW || am == A_IM2COL_T || am == A_COL)) return 64;
+  return cfg == CFG_64_64_64 && (am == A_IM2COL || am == A_ROW || am == A_IM2COL_T) ? 64 : 0;
+}
+template <typename T>
+constexpr int staged_bk(int am, int cfg) { return staged_bkt<T>(am, cfg) ? staged_bkt<T>(am, cfg) : TT<T>::BK; }
 
 template <typename T, int AM, int BMODE>
 static int launch_cfg(int cfg, GemmParams& p, int batch, bool vec, hipStream_t s) {
-  constexpr bool F32 = std::is_same<T, float>::value;
   switch (cfg) {
-    case CFG_128_128_64:
-      if constexpr (!F32 && (AM == A_IM2COL || AM == A_ROW || AM == A_IM2COL_T || AM == A_COL))
-        return launch_one<T, 128, 128, 2, 2, AM, BMODE, 64>(p, batch, vec, s);
-      return launch_one<T, 128, 128, 2, 2, AM, BMODE, 0>(p, batch, vec, s);
-    case CFG_64_64_64:
-      if constexpr (!F32 && (AM == A_IM2COL || AM == A_ROW || AM == A_IM2COL_T))
-        return launch_one<T, 64, 64, 2, 2, AM, BMODE, 64>(p, batch, vec, s);
-      return launch_one<T, 64, 64, 2, 2, AM, BMODE, 0>(p, batch, vec, s);
+    case CFG_128_128_64: return launch_one<T, 128, 128, 2, 2, AM, BMODE, staged_bkt<T>(AM, CFG_128_128_64)>(p, batch, vec, s);
+    case CFG_64_64_64: return launch_one<T, 64, 64, 2, 2, AM, BMODE, staged_bkt<T>(AM, CFG_64_64_64)>(p, batch, vec, s);
     case CFG_128_128_32: return launch_one<T, 128, 128, 2, 2, AM, BMODE, 0>(p, batch, vec, s);
     case CFG_32_32_32: return launch_one<T, 32, 32, 1, 1, AM, BMODE, 0>(p, batch, vec, s);
     default: return launch_one<T, 64, 64, 2, 2, AM, BMODE, 0>(p, batch, vec, s);
@@ -190,6 +201,19 @@ static int choose_cfg(int amode, int bmode, int M, int N, int K, long long batch
 // after the launch, when split= is its split count too; cfg 111: the same
 // launch queued in a deferred region, run by a grouped launch, cfg 112 with
 // jobs= blocks= tile= of that launch)
+// The cfg= codes above the CFG_* tile configs. The three pipe routes add the
+// tile class (PipePlan::cfg, 0-11): 160 + 10 / 11 print the same number as
+// 170 + 0 / 1 and the c= field tells them apart.
+enum GemmRoute {
+  ROUTE_PIPE_WG = 110,         // pipelined weight gradient, launched
+  ROUTE_PIPE_WG_QUEUED = 111,  // the same launch queued for the deferred flush
+  ROUTE_WG_JOBS = 112,         // the flush's grouped launch of the queued ones (gemm_bf16.hip)
+  ROUTE_PIPE = 130,            // LDS-DMA pipe kernel
+  ROUTE_DENSE_JOB = 150,       // Dense weight gradient queued as a whole-K job
+  ROUTE_SCATTER_PIPE = 160,    // C_SCATTER rows: pipe kernel + scatter_rows_kernel
+  ROUTE_TALL_ROWS = 170,       // tall row GEMM as a 1x1 implicit GEMM on the pipe kernel
+};
+
 template <typename T>
 static void log_gemm(const GemmParams& p, int batch, int amode, int bmode, int cfg, int psplit = 0) {
   if (FILE* f = gemm_log()) {
@@ -197,7 +221,7 @@ static void log_gemm(const GemmParams& p, int batch, int amode, int bmode, int c
                  std::is_same<T, float>::value ? "f32" : "bf16", amode, bmode, p.c_mode, p.M, p.N, p.K, batch,
                  p.accumulate, p.split_k, cfg);
     if (psplit > 0) std::fprintf(f, " psplit=%d", psplit);
-    if (cfg == 110 || cfg == 111) std::fprintf(f, " tm=%d tn=%d", p.tiles_m, p.tiles_n);
+    if (cfg == ROUTE_PIPE_WG || cfg == ROUTE_PIPE_WG_QUEUED) std::fprintf(f, " tm=%d tn=%d", p.tiles_m, p.tiles_n);
     std::fputc('\n', f);
     std::fflush(f);
   }
@@ -271,10 +295,7 @@ static int launch_wgrad_reduce(const GemmParams& p, int batch, const float* base
   const long long items = (long long)p.M * cdiv(p.N, 4) * batch;
   const int G = items >= 256 * 256 ? 1 : (p.split_k >= 8 ? 16 : p.split_k >= 4 ? 4 : 1);
   if (defer_owns(base)) return defer_wgrad(p, base, batch, G, s);
-  {
-    const int st = touch_c(p, batch, s);
-    if (st) return st;
-  }
+  if (const int st = touch_c(p, batch, s)) return st;
   if (G == 16) wgrad_reduce_g<16>(p, batch, base, s);
   else if (G == 4) wgrad_reduce_g<4>(p, batch, base, s);
   else wgrad_reduce_g<1>(p, batch, base, s);
@@ -322,20 +343,10 @@ static bool pipe_eligible(const GemmParams& p, int batch, int amode, int bmode, 
 }
 
 // splits > 1: split-K over grid.y; p is then the partial-slab form (see
-// launch_pipe_split) and k_per_split K-tiles * 64 per split
+// launch_pipe_plan) and k_per_split K-tiles * 64 per split
 template <int BM, int BN, int WM, int WN, int AM, int NT, int STAGES, int EPI, int SPREAD = 0, int MF = 32>
 static int launch_pipe(GemmParams& p, int batch, int splits, hipStream_t s) {
-  if (p.ngroups > 0) {
-    int t = 0;
-    for (int g = 0; g < p.ngroups; ++g) {
-      p.groups[g].start = t;
-      t += cdiv(p.groups[g].M, BM);
-    }
-    p.tiles_m = t;
-  } else {
-    p.tiles_m = cdiv(p.M, BM);
-  }
-  p.tiles_n = cdiv(p.N, BN);
+  set_tile_grid(p, BM, BN);
   p.split_k = splits;
   if (splits <= 1) p.k_per_split = p.K;
   p.zero16 = g_split_ws.zero;
@@ -348,17 +359,7 @@ static int launch_pipe(GemmParams& p, int batch, int splits, hipStream_t s) {
 // conventions as launch_pipe, WM * WN + NLW waves per block
 template <int BM, int BN, int WM, int WN, int AM, int NLW, int STAGES, int MS = BM>
 static int launch_pipe_lw(GemmParams& p, int batch, int splits, hipStream_t s) {
-  if (p.ngroups > 0) {
-    int t = 0;
-    for (int g = 0; g < p.ngroups; ++g) {
-      p.groups[g].start = t;
-      t += cdiv(p.groups[g].M, MS);
-    }
-    p.tiles_m = t;
-  } else {
-    p.tiles_m = cdiv(p.M, MS);
-  }
-  p.tiles_n = cdiv(p.N, BN);
+  set_tile_grid(p, MS, BN);
   p.split_k = splits;
   if (splits <= 1) p.k_per_split = p.K;
   p.zero16 = g_split_ws.zero;
@@ -413,14 +414,6 @@ static int launch_pipe_lw(GemmParams& p, int batch, int splits, hipStream_t s) {
 //     With the loader waves the 128x256 tile also takes the K >= 1024 1x1
 //     convs once they fill the chip (C3's res4 1x1 1024->256 at 32^2 62.8 ->
 //     52.9 us, res5 1x1 2048->512 at 16^2 49.0 -> 42.0; profiles/r06/c3_shapes.txt).
-// M tiles of the launch at M step ms (grouped launches: per group)
-static long long m_tiles(const GemmParams& p, int ms) {
-  if (p.ngroups <= 0) return cdiv(p.M, ms);
-  long long t = 0;
-  for (int g = 0; g < p.ngroups; ++g) t += cdiv(p.groups[g].M, ms);
-  return t;
-}
-
 //   * round 6, the wide class's tile count: 128x256 tiles leave CUs idle when
 //     the launch's tiles fill a wave of blocks unevenly (C2 P3, M = 25 088: 196
 //     tiles on 256 CUs). An M step of 112 rows (cfg 10: the same 128x256 LDS
@@ -428,22 +421,23 @@ static long long m_tiles(const GemmParams& p, int ms) {
 //     zero chunk) puts it on 224 tiles; taken where it leaves fewer output
 //     rows per CU over the launch's waves of blocks (112 x ceil(t112 / CUs)
 //     against 128 x ceil(t128 / CUs)). Measured against cfg 6 on one box
-//     (bench.py --roofline-only, FPNMT_WIDE_CFG; profiles/r06/wide_tiles.txt):
+//     (bench.py --roofline-only, the tile forced; profiles/r06/wide_tiles.txt):
 //     42.1-42.6 -> 41.2-41.9 us by HIP events, 40.98 -> 40.37 us rocprofv3
 //     average; headline forward 1.918 -> 1.905 ms. Lost: 224x128 (4 loaders, 2
 //     x 4 waves of 112 x 32) 43.5-44.2 us, 208x128 (2 loaders, 1 x 8 of 208 x
 //     16) 55.4-56.8 and 112x256 with 2 loaders (no zero rows) 47.8-48.4,
 //     although the first two move fewer L2 -> LDS bytes per CU.
-//     FPNMT_WIDE_CFG=6|10 forces one (A/B probes, the bitwise test).
-static int wide_cfg(const GemmParams& p, int batch) {
-  const char* e = std::getenv("FPNMT_WIDE_CFG");
-  if (e && e[0]) {
-    const int f = std::atoi(e);
-    if (f == 6 || f == 10) return f;
-  }
-  const long long cus = cu_count_dispatch(), tn = (long long)cdiv(p.N, 256) * batch;
+//     fpnmt_set_wide_cfg(6 | 10) forces one (A/B probes, the bitwise test).
+// the 112-row M step leaves fewer output rows per CU over the launch's waves of blocks (tiles bn wide)
+static bool m112_fewer_rows(const GemmParams& p, int batch, int bn) {
+  const long long cus = cu_count_dispatch(), tn = (long long)cdiv(p.N, bn) * batch;
   const long long w128 = (m_tiles(p, 128) * tn + cus - 1) / cus, w112 = (m_tiles(p, 112) * tn + cus - 1) / cus;
-  return 112 * w112 < 128 * w128 ? 10 : 6;
+  return 112 * w112 < 128 * w128;
+}
+
+static int wide_cfg(const GemmParams& p, int batch) {
+  if (const int f = forced_wide_cfg()) return f;
+  return m112_fewer_rows(p, batch, 256) ? 10 : 6;
 }
 
 static int pipe_cfg(const GemmParams& p, int batch) {
@@ -456,32 +450,49 @@ static int pipe_cfg(const GemmParams& p, int batch) {
   if (tiles < 1024 && nk >= 32 && p.N >= 256) {
     // the 128x128 loader tile at the same 112-row M step (cfg 11: 1 x 4 MFMA
     // waves of 112 x 32) where it leaves fewer rows per CU (res4's 3x3: 196
-    // tiles at batch 64, 98 at 32); FPNMT_WIDE_CFG=6 keeps the 128-row step
-    const char* e = std::getenv("FPNMT_WIDE_CFG");
-    const long long cus = cu_count_dispatch(), tn = (long long)cdiv(p.N, 128) * batch;
-    const long long w128 = (m_tiles(p, 128) * tn + cus - 1) / cus, w112 = (m_tiles(p, 112) * tn + cus - 1) / cus;
-    return !(e && e[0] == '6') && 112 * w112 < 128 * w128 ? 11 : 7;
+    // tiles at batch 64, 98 at 32); fpnmt_set_wide_cfg(6) keeps the 128-row
+    // step, 10 leaves this class automatic
+    return forced_wide_cfg() != 6 && m112_fewer_rows(p, batch, 128) ? 11 : 7;
   }
   if (tiles < 1024 && nk >= 8) return 2;
   return 1;
 }
 
+// The (operand mode, tile class) pairs a dispatch rule can return, the only
+// ones instantiated: pipe_cfg's 0 1 2 6 7 8 10 11 on A_IM2COL (convs, scatter
+// and tall-row reroutes); 3 and row_short_cfg's 5 8 9 on A_ROW; 4 (64x64,
+// 4-stage spread ring) nowhere. FPNMT_PIPE_ALL_CFGS (tools/fwd_bench.hip only,
+// never the library) instantiates every class for the tool's forced tiles.
+template <int AM>
+constexpr bool pipe_cfg_built(int cfg) {
+#ifdef FPNMT_PIPE_ALL_CFGS
+  return true;
+#endif
+  if (AM == A_IM2COL) return cfg == 0 || cfg == 1 || cfg == 2 || cfg == 6 || cfg == 7 || cfg == 8 || cfg == 10 || cfg == 11;
+  if (AM == A_ROW) return cfg == 3 || cfg == 5 || cfg == 8 || cfg == 9;
+  return false;
+}
+
 template <int AM>
 static int launch_pipe_cfg(int cfg, GemmParams& p, int batch, int splits, hipStream_t s) {
+#define FPNMT_PIPE_CASE(c, ...) \
+  case c: if constexpr (pipe_cfg_built<AM>(c)) return __VA_ARGS__(p, batch, splits, s); break;
   switch (cfg) {
-    case 0: return launch_pipe<128, 64, 4, 1, AM, 256, 1, 0>(p, batch, splits, s);
-    case 2: return launch_pipe<64, 64, 2, 2, AM, 256, 2, 1, 0, 16>(p, batch, splits, s);
-    case 3: return launch_pipe<128, 256, 2, 4, AM, 512, 3, 1, 2, 16>(p, batch, splits, s);
-    case 4: return launch_pipe<64, 64, 2, 2, AM, 256, 4, 1, 1>(p, batch, splits, s);
-    case 5: return launch_pipe<64, 32, 2, 2, AM, 256, 4, 1, 1, 16>(p, batch, splits, s);
-    case 6: return launch_pipe_lw<128, 256, 2, 4, AM, 4, 3>(p, batch, splits, s);
-    case 7: return launch_pipe_lw<128, 128, 2, 2, AM, 4, 3>(p, batch, splits, s);
-    case 8: return launch_pipe_lw<64, 64, 2, 2, AM, 4, 4>(p, batch, splits, s);
-    case 9: return launch_pipe_lw<64, 32, 2, 2, AM, 2, 4>(p, batch, splits, s);
-    case 10: return launch_pipe_lw<128, 256, 1, 8, AM, 4, 3, 112>(p, batch, splits, s);
-    case 11: return launch_pipe_lw<128, 128, 1, 4, AM, 4, 3, 112>(p, batch, splits, s);
-    default: return launch_pipe<64, 64, 2, 2, AM, 256, 1, 1>(p, batch, splits, s);
+    FPNMT_PIPE_CASE(0, launch_pipe<128, 64, 4, 1, AM, 256, 1, 0>)
+    FPNMT_PIPE_CASE(1, launch_pipe<64, 64, 2, 2, AM, 256, 1, 1>)
+    FPNMT_PIPE_CASE(2, launch_pipe<64, 64, 2, 2, AM, 256, 2, 1, 0, 16>)
+    FPNMT_PIPE_CASE(3, launch_pipe<128, 256, 2, 4, AM, 512, 3, 1, 2, 16>)
+    FPNMT_PIPE_CASE(4, launch_pipe<64, 64, 2, 2, AM, 256, 4, 1, 1>)
+    FPNMT_PIPE_CASE(5, launch_pipe<64, 32, 2, 2, AM, 256, 4, 1, 1, 16>)
+    FPNMT_PIPE_CASE(6, launch_pipe_lw<128, 256, 2, 4, AM, 4, 3>)
+    FPNMT_PIPE_CASE(7, launch_pipe_lw<128, 128, 2, 2, AM, 4, 3>)
+    FPNMT_PIPE_CASE(8, launch_pipe_lw<64, 64, 2, 2, AM, 4, 4>)
+    FPNMT_PIPE_CASE(9, launch_pipe_lw<64, 32, 2, 2, AM, 2, 4>)
+    FPNMT_PIPE_CASE(10, launch_pipe_lw<128, 256, 1, 8, AM, 4, 3, 112>)
+    FPNMT_PIPE_CASE(11, launch_pipe_lw<128, 128, 1, 4, AM, 4, 3, 112>)
   }
+#undef FPNMT_PIPE_CASE
+  return fail(FPNMT_E_UNSUPPORTED, "gemm: pipe tile class " + std::to_string(cfg) + " not instantiated for this operand mode");
 }
 
 // Fewer than 128 tiles over a long K (P7 of the batch-64 forward): S partial
@@ -494,53 +505,44 @@ static int launch_pipe_cfg(int cfg, GemmParams& p, int batch, int splits, hipStr
 static int pipe_split_for(const GemmParams& p, int batch) {
   if (!g_split_ws.part || batch != 1 || p.accumulate != 0) return 1;
   const int nkt = p.K / 64;
-  long long tiles = 0;
-  if (p.ngroups > 0)
-    for (int g = 0; g < p.ngroups; ++g) tiles += cdiv(p.groups[g].M, 64);
-  else
-    tiles = cdiv(p.M, 64);
-  tiles *= cdiv(p.N, 64);
+  const long long tiles = (long long)m_tiles(p, 64) * cdiv(p.N, 64);
   if (tiles >= 128 || nkt < 16) return 1;
-  int S = (int)((256 + tiles - 1) / tiles);
-  S = std::min(S, nkt / 8);
-  S = std::min(S, 8);
-  while (S > 1 && (long long)S * p.M * p.N > g_split_ws.part_floats) --S;
-  return S < 2 ? 1 : S;
+  return std::min({(int)((256 + tiles - 1) / tiles), nkt / 8, 8});
 }
 
-// the split count launch_pipe_auto runs p with (the log's psplit= field):
-// pipe_split_for's choice after launch_pipe_split's no-empty-split rounding
-static int pipe_split_logged(const GemmParams& p, int batch) {
-  int S = pipe_split_for(p, batch);
-  if (S <= 1) return 1;
+// the most splits (<= S) whose M x N fp32 slabs fit the workspace
+static int ws_fit_splits(int S, const GemmParams& p) {
+  while (S > 1 && (long long)S * p.M * p.N > g_split_ws.part_floats) --S;
+  return S;
+}
+
+// What an LDS-DMA pipe launch will do, decided once: the log prints it and
+// launch_pipe_plan runs it. cfg: the tile class (launch_pipe_cfg); splits: 1 =
+// one direct launch, > 1 = partial slabs + ordered reduce; kt_per: K-tiles of
+// 64 per split.
+struct PipePlan { int cfg, splits, kt_per; };
+
+// tile class cfg at up to S splits: S after the workspace fit, at most one per
+// K-tile, and rounded so that no split is empty (every slab is written)
+static PipePlan pipe_plan_split(int cfg, int S, const GemmParams& p) {
   const int nkt = p.K / 64;
-  while (S > 1 && (long long)S * p.M * p.N > g_split_ws.part_floats) --S;
-  if (S > nkt) S = nkt;
-  return cdiv(nkt, cdiv(nkt, std::max(S, 1)));
+  S = std::min(ws_fit_splits(S, p), nkt);
+  if (S < 2) return {cfg, 1, nkt};
+  const int kt_per = cdiv(nkt, S);
+  return {cfg, cdiv(nkt, kt_per), kt_per};
 }
 
-template <int AM>
-static int launch_pipe_split(int cfg, int S, const GemmParams& p, hipStream_t s) {
+// Split-K through the workspace: launch(q) runs p as `splits` raw fp32 slabs
+// ws[split][m][n] without epilogue, gemm_splitk_reduce_kernel then runs p's
+// epilogue on their split-ordered sum. (r_mask goes with R: a no-op, every
+// kernel reads it only beside a non-null R.)
+template <typename T, typename Launch>
+static int launch_ws_split(const GemmParams& p, int splits, int k_per_split, hipStream_t s, Launch launch) {
   GemmParams q = p;
-  const int nkt = p.K / 64;
-  while (S > 1 && (long long)S * p.M * p.N > g_split_ws.part_floats) --S;  // the slabs fit the workspace
-  if (S > nkt) S = nkt;
-  const int kt_per = cdiv(nkt, std::max(S, 1));
-  S = cdiv(nkt, kt_per);  // no empty split: every slab is written
-  q.k_per_split = kt_per * 64;
-  q.bias = nullptr;
-  q.col_scale = nullptr;
-  q.R = nullptr;
-  q.r_mask = 0;
-  q.act = FPNMT_ACT_NONE;
-  q.drop_p = 0.f;
-  q.drop_seed_dev = nullptr;
-  q.alpha = 1.f;
-  q.c_f32 = 1;
-  q.accumulate = 0;
-  q.C = g_split_ws.part;
-  q.ldc = p.N;
-  q.c_so = q.c_si = 0;
+  q.split_k = splits; q.k_per_split = k_per_split;
+  q.bias = nullptr; q.col_scale = nullptr; q.R = nullptr; q.r_mask = 0; q.act = FPNMT_ACT_NONE;
+  q.drop_p = 0.f; q.drop_seed_dev = nullptr; q.alpha = 1.f; q.c_f32 = 1; q.accumulate = 0;
+  q.C = g_split_ws.part; q.ldc = p.N; q.c_so = q.c_si = 0;
   q.c_split = (long long)p.M * p.N;  // p.M = the groups' rows in total
   RowOffsets ro{};
   for (int g = 0, r = 0; g < p.ngroups; ++g) {  // groups' slab rows back to back
@@ -550,11 +552,11 @@ static int launch_pipe_split(int cfg, int S, const GemmParams& p, hipStream_t s)
     r += p.groups[g].M;
     ro.off[g + 1] = r;
   }
-  const int st = launch_pipe_cfg<AM>(cfg, q, 1, S, s);
+  const int st = launch(q);
   if (st) return st;
   const long long items = (long long)p.M * cdiv(p.N, 4);
-  hipLaunchKernelGGL((gemm_splitk_reduce_kernel<bf16>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p,
-                     (const float*)g_split_ws.part, S, ro);
+  hipLaunchKernelGGL((gemm_splitk_reduce_kernel<T>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p,
+                     (const float*)g_split_ws.part, splits, ro);
   return check_launch("gemm_splitk_reduce_kernel");
 }
 
@@ -573,19 +575,29 @@ static int row_short_cfg(const GemmParams& p) {
   return 8;
 }
 
-template <int AM>
-static int launch_pipe_auto(GemmParams& p, int batch, hipStream_t s) {
+// The plan of a pipe_eligible launch (amode A_ROW or A_IM2COL). Reads the
+// workspace size; launches nothing, allocates nothing, leaves p alone.
+// splits == 1 ("the pipe kernel's own epilogue runs": the M2 mask and the
+// scatter / tall-row reroutes ask it) exactly when pipe_split_for's count is
+// below 2 after the workspace fit: a surviving S has 2 <= S <= min(8, nkt / 8),
+// so kt_per = ceil(nkt / S) < nkt and the rounding ceil(nkt / kt_per) stays >= 2.
+static PipePlan pipe_plan(const GemmParams& p, int batch, int amode) {
   // short rows: the 4-stage 64x64 ring (measured against 1 / 2 / 6 / 8
   // stages and a split-K of 2); up to N = 1536 on 64x32
   // tiles with 16x16x32 MFMA, twice the blocks on the same rows
   // (tools/small_bench.hip -DSB_PIPE, profiles/r05/small_pipe_r5h2.txt,
   // M = 992: N 512 K 512 6.73 -> 5.62 us, K 2048 14.22 -> 12.02, N 1536
   // 8.36 -> 7.55; N 2048 stays on 64x64: 8.64 against 10.76)
-  const bool row_short = AM == A_ROW && pipe_row_short(p, batch);
-  const int cfg = AM == A_ROW ? (row_short ? row_short_cfg(p) : 3) : pipe_cfg(p, batch);
-  const int S = pipe_split_for(p, batch);
-  if (S > 1) return launch_pipe_split<AM>(cfg, S, p, s);
-  return launch_pipe_cfg<AM>(cfg, p, batch, 1, s);
+  const int cfg = amode == A_ROW ? (pipe_row_short(p, batch) ? row_short_cfg(p) : 3) : pipe_cfg(p, batch);
+  return pipe_plan_split(cfg, pipe_split_for(p, batch), p);
+}
+
+template <int AM>
+static int launch_pipe_plan(const PipePlan& plan, GemmParams& p, int batch, hipStream_t s) {
+  if (plan.splits <= 1) return launch_pipe_cfg<AM>(plan.cfg, p, batch, 1, s);
+  return launch_ws_split<bf16>(p, plan.splits, plan.kt_per * 64, s, [&](GemmParams& q) {
+    return launch_pipe_cfg<AM>(plan.cfg, q, 1, plan.splits, s);  // split only at batch 1
+  });
 }
 
 // Weight gradients (fp32 atomics into the arena) of the wide convs / Dense
@@ -609,15 +621,10 @@ static bool pipe_wg_eligible(const GemmParams& p, int batch, int amode, int bmod
   } else {
     return false;
   }
-  long long kt = 0;
-  if (p.ngroups > 0)
-    for (int g = 0; g < p.ngroups; ++g) kt += (p.groups[g].K + 63) / 64;
-  else
-    kt = (p.K + 63) / 64;
   // >= 1024 reduction rows: the res5 weight gradients (K = 1568 at batch 32)
   // gain too (r5 3x3 on 256x128 24.7 us against 30.5; r5 1x1 on 128x128 12.1 /
   // 12.5 against 14.3 / 13.7)
-  return kt >= 16;
+  return k_tiles(p, 64) >= 16;
 }
 
 // The kernel instantiations with a grouped form (gemm_pipe_wg_jobs_kernel;
@@ -637,8 +644,7 @@ constexpr int wg_job_class() {
 // A split conv weight gradient inside a deferred region whose slabs (and
 // folded bias partials) lie in the arena: queued, run at the flush (the
 // caller holds x and dz until then: fpnmt_set_defer_conv_wgrads). q: the
-// launch's slab params. g_wg_queued tells the dispatcher's log.
-static bool g_wg_queued = false;
+// launch's slab params.
 static bool wg_conv_job_ok(const GemmParams& q, int cls) {
   if (cls < 0 || !conv_wgrad_entry() || !((conv_wgrad_classes() >> cls) & 1) || !defer_active()) return false;
   if (q.ngroups > 0 || q.split_k <= 1 || !defer_owns(q.C) || (q.cs_part && !defer_owns(q.cs_part))) return false;
@@ -658,8 +664,9 @@ static int defer_conv_job(const GemmParams& q, int cls) {
   return defer_conv_wg(J);
 }
 
+// queued: the launch went to the deferred queue (ROUTE_PIPE_WG_QUEUED in the log)
 template <int AM, int BM, int BN, int WM, int WN, int NLW = 0>
-static int launch_pipe_wg_t(GemmParams& p, hipStream_t s) {
+static int launch_pipe_wg_t(GemmParams& p, hipStream_t s, bool& queued) {
   constexpr int BK = 64;
   p.tiles_m = cdiv(p.M, BM);
   p.tiles_n = cdiv(p.N, BN);
@@ -670,15 +677,7 @@ static int launch_pipe_wg_t(GemmParams& p, hipStream_t s) {
   // evenly across group boundaries (gemm_pipe_wg_kernel).
   const long long cus = cu_count_dispatch();
   const long long want = std::max<long long>(1, cus / tiles);
-  long long tot_kt = 0;
-  if (p.ngroups > 0) {
-    for (int g = 0; g < p.ngroups; ++g) {
-      p.groups[g].start = (int)tot_kt;
-      tot_kt += cdiv(p.groups[g].K, BK);
-    }
-  } else {
-    tot_kt = cdiv(p.K, BK);
-  }
+  const long long tot_kt = group_tiles(p, true, BK, p.groups);
   long long kt_per = std::max<long long>(4, (tot_kt + want - 1) / want);
   // more than one split: partial slabs + ordered reduce (deterministic);
   // fewer, longer splits when the slabs would not fit the workspace
@@ -712,7 +711,7 @@ static int launch_pipe_wg_t(GemmParams& p, hipStream_t s) {
     constexpr int cls = wg_job_class<AM, BM, BN, WM, WN, NLW>();
     if (wg_conv_job_ok(q, cls)) {  // the same blocks, in a grouped launch at the flush
       st = defer_conv_job(q, cls);
-      g_wg_queued = true;
+      queued = true;
     } else {
       hipLaunchKernelGGL((gemm_pipe_wg_kernel<BM, BN, WM, WN, AM, 0, 32, NLW>), grid, dim3(64 * (WM * WN + NLW)), 0,
                          s, q);
@@ -721,31 +720,26 @@ static int launch_pipe_wg_t(GemmParams& p, hipStream_t s) {
     if (!st) st = launch_wgrad_reduce(p, 1, base, s);
     return st ? st : fold_bias();
   }
-  {
-    const int st = touch_c(p, 1, s);
-    if (st) return st;
-  }
+  if (const int st = touch_c(p, 1, s)) return st;
   hipLaunchKernelGGL((gemm_pipe_wg_kernel<BM, BN, WM, WN, AM, 0, 32, NLW>), grid, dim3(64 * (WM * WN + NLW)), 0, s, p);
   const int st = check_launch("gemm_pipe_wg_kernel");
   return st ? st : fold_bias();
 }
 
+// Only the (operand mode, tile form) pairs a rule can pick are instantiated: 128x256
+// + 8 loader waves and plain 128x128 on A_IM2COL_T, 128x128 + 4 loader waves on A_COL.
 template <int AM>
-static int launch_pipe_wg(GemmParams& p, hipStream_t s) {
+static int launch_pipe_wg(GemmParams& p, hipStream_t s, bool& queued) {
   // 256x128 halves the dz re-reads on the long reductions (grouped P3-P7
   // head wgrad, M=2304 K=33248: 116 -> 103 us) but is slower on short ones
   // (K=6272: 32 -> 41 us) and on few m-tiles; 128x128 with 8 waves otherwise
   // (measured faster than 4 waves)
-  long long kt = 0;
-  if (p.ngroups > 0)
-    for (int g = 0; g < p.ngroups; ++g) kt += (p.groups[g].K + 63) / 64;
-  else
-    kt = (p.K + 63) / 64;
+  const long long kt = k_tiles(p, 64);
   // 64-wide sides (8-chunk LDS rows, round 5, profiles/r05/wg_w64.txt): N = 64
   // (res2 1x1 256->64: 18.1 us against 20.5 on the 64x64 kernel) on 128x64,
   // M = 64 (res2 1x1 64->256: 18.6 against 20.6) on 64x256
-  if (p.N < 128) return launch_pipe_wg_t<AM, 128, 64, 2, 2>(p, s);
-  if (p.M < 128) return launch_pipe_wg_t<AM, 64, 256, 1, 4>(p, s);
+  if (p.N < 128) return launch_pipe_wg_t<AM, 128, 64, 2, 2>(p, s, queued);
+  if (p.M < 128) return launch_pipe_wg_t<AM, 64, 256, 1, 4>(p, s, queued);
   // conv weight gradients with N >= 256 over >= 1024 rows: 128x256 (half the
   // im2col^T rows per block, whose per-chunk tap gathers are the costly DMA
   // side) — tools/wg_bench.hip -DWB_HALO (profiles/r05/wg_halo.txt): P3 head
@@ -764,11 +758,12 @@ static int launch_pipe_wg(GemmParams& p, hipStream_t s) {
   // 4 loader waves 11.7 -> 11.3 us (r3 1x1 13.0 -> 11.9); the 3x3 128x128 and
   // the 256x128 tiles measured equal or slower with loaders and stay
   const bool wide = p.M >= 1024 && (kt >= 128 || p.M >= 4096) && (AM != A_IM2COL_T || p.Cc % 256 == 0);
-  if (AM == A_IM2COL_T && p.N >= 256 && p.M >= 1024 && (wide || p.N >= 512))
-    return launch_pipe_wg_t<AM, 128, 256, 2, 4, 8>(p, s);
-  if (wide) return launch_pipe_wg_t<AM, 256, 128, 4, 2>(p, s);
-  if (AM == A_COL) return launch_pipe_wg_t<AM, 128, 128, 2, 4, 4>(p, s);
-  return launch_pipe_wg_t<AM, 128, 128, 2, 4>(p, s);
+  if constexpr (AM == A_IM2COL_T) {
+    if (p.N >= 256 && p.M >= 1024 && (wide || p.N >= 512)) return launch_pipe_wg_t<AM, 128, 256, 2, 4, 8>(p, s, queued);
+  }
+  if (wide) return launch_pipe_wg_t<AM, 256, 128, 4, 2>(p, s, queued);
+  constexpr int NLW = AM == A_COL ? 4 : 0;  // 128x128: 4 loader waves on the 1x1 / Dense operand only
+  return launch_pipe_wg_t<AM, 128, 128, 2, 4, NLW>(p, s, queued);
 }
 
 template <typename T>
@@ -799,10 +794,7 @@ static int ws_split_for(const GemmParams& p, int batch, int cfg, int BK) {
   // M=6272 N=256 K=1024 (392 blocks, 16 K-tiles) 20.7 -> 28.3 us (slower)
   // M=6272 N=256 K=2304 (392 blocks, 36 K-tiles) 36.6 -> 33.1 us
   if (!((blocks < 320 && nkt >= 24) || (blocks < 512 && nkt >= 32))) return 1;
-  int S = (int)((768 + blocks - 1) / blocks);
-  S = std::min(S, nkt / 8);
-  S = std::min(S, 8);
-  while (S > 1 && (long long)S * p.M * p.N > g_split_ws.part_floats) --S;
+  const int S = ws_fit_splits(std::min({(int)((768 + blocks - 1) / blocks), nkt / 8, 8}), p);
   return S < 2 ? 1 : S;
 }
 
@@ -823,13 +815,7 @@ template <typename T>
 int dispatch_gemm_impl(GemmParams& p, int batch, int amode, int bmode, bool vec, hipStream_t s);
 
 template <typename T>
-static int dispatch_with_m2(GemmParams& p, int batch, int amode, int bmode, bool vec, hipStream_t s) {
-  if (batch != 1 || p.accumulate == 2 || p.c_f32 || p.ngroups > 0)
-    return fail(FPNMT_E_UNSUPPORTED, "gemm: the M2 mask needs batch 1, bf16 C, no atomics");
-  // scattered rows (strided 1x1 bwd-data) only reach the register-staged
-  // kernel, whose row epilogue applies M2 at the scattered row
-  if (p.c_mode == C_SCATTER) return 1;
-  if (pipe_eligible<T>(p, batch, amode, bmode, vec) && pipe_split_for(p, batch) == 1) return 1;  // the pipe epilogue applies M2
+static int dispatch_m2_unfused(GemmParams& p, int batch, int amode, int bmode, bool vec, hipStream_t s) {
   GemmParams q = p;
   q.M2 = nullptr;
   const int st = dispatch_gemm_impl<T>(q, batch, amode, bmode, vec, s);
@@ -913,27 +899,34 @@ static __global__ __launch_bounds__(256) void scatter_rows_kernel(const GemmPara
   *(bf16x8*)Cp = o;
 }
 
-// the pipe form of a C_SCATTER GEMM when every operand allows it (1 = not taken)
-static int scatter_via_pipe(const GemmParams& p, int batch, int amode, int bmode, bool vec, hipStream_t s) {
+// a GEMM rerouted to the conv pipe classes: q, the launch as a 1x1 implicit GEMM over its rows, and q's plan
+struct PipeReroute { GemmParams q; PipePlan plan; };
+
+// q's rows as a 1-wide image of M rows and K channels under a 1x1 filter
+static void rows_as_image(GemmParams& q) {
+  q.H = q.Ho = q.M; q.W = q.Wo = 1; q.Cc = q.K; q.Rk = q.Sk = 1; q.sh = q.sw = 1; q.pt = q.pl = 0;
+  q.fd_HoWo = make_fastdiv(q.M); q.fd_Wo = make_fastdiv(1); q.fd_C = make_fastdiv(q.K); q.fd_S = make_fastdiv(1);
+}
+
+// the pipe form of a C_SCATTER GEMM, when every operand allows it
+static bool scatter_reroute(const GemmParams& p, int batch, int amode, int bmode, bool vec, PipeReroute& r) {
   if (batch != 1 || amode != A_ROW || bmode != B_NK || p.bias || p.R || p.act != FPNMT_ACT_NONE ||
       p.drop_p > 0.f || p.alpha != 1.f || p.col_scale || p.c_f32 || (p.accumulate != 0 && p.accumulate != 1) ||
       p.ngroups > 0 || p.K % 64 || p.N % 8 || p.ldc % 8 || (p.M2 && p.ldr % 8))
-    return 1;
+    return false;
   if ((((uintptr_t)p.C | (uintptr_t)p.M2) & 15) || !g_split_ws.part || (long long)p.M * p.N > g_split_ws.part_floats)
-    return 1;
-  GemmParams q = p;  // dz rows as a 1x1 implicit GEMM (a 1-wide image of M rows)
-  q.c_mode = C_ROW;
-  q.M2 = nullptr;
-  q.c_f32 = 1;
-  q.accumulate = 0;
-  q.C = g_split_ws.part;
-  q.ldc = p.N;
-  q.c_so = q.c_si = 0;
-  q.H = q.Ho = p.M; q.W = q.Wo = 1; q.Cc = p.K; q.Rk = q.Sk = 1; q.sh = q.sw = 1; q.pt = q.pl = 0;
-  q.fd_HoWo = make_fastdiv(p.M); q.fd_Wo = make_fastdiv(1); q.fd_C = make_fastdiv(p.K); q.fd_S = make_fastdiv(1);
-  if (!pipe_eligible<bf16>(q, 1, A_IM2COL, B_NK, vec) || pipe_split_for(q, 1) != 1) return 1;
-  log_gemm<bf16>(p, batch, amode, bmode, 160 + pipe_cfg(q, 1), pipe_split_logged(q, 1));
-  const int st = launch_pipe_auto<A_IM2COL>(q, 1, s);
+    return false;
+  GemmParams& q = r.q = p;  // dz rows as a 1x1 implicit GEMM into fp32 rows in the workspace
+  q.c_mode = C_ROW; q.M2 = nullptr; q.c_f32 = 1; q.accumulate = 0;
+  q.C = g_split_ws.part; q.ldc = p.N; q.c_so = q.c_si = 0;
+  rows_as_image(q);
+  if (!pipe_eligible<bf16>(q, 1, A_IM2COL, B_NK, vec)) return false;
+  r.plan = pipe_plan(q, 1, A_IM2COL);
+  return r.plan.splits == 1;  // a split's slabs would take the workspace rows
+}
+
+static inline int launch_scatter_reroute(const GemmParams& p, PipeReroute& r, hipStream_t s) {
+  const int st = launch_pipe_plan<A_IM2COL>(r.plan, r.q, 1, s);
   if (st) return st;
   const long long items = (long long)p.M * (p.N / 8);
   hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p,
@@ -945,91 +938,47 @@ static int scatter_via_pipe(const GemmParams& p, int batch, int amode, int bmode
 // 128 tiles of 128x256: the encoder views' K / V projection dgrads, M = 6272,
 // N = 512, K = 6144 at C2) as a 1x1 implicit GEMM over the A rows, which the
 // conv pipe classes tile by their own tile-count rules (128x128 loader tile
-// there) instead of the register-staged 64x64 kernel. Same epilogue fields;
-// 1 = not taken.
-template <typename T>
-static int rows_via_im2col(GemmParams& p, int batch, int amode, int bmode, bool vec, hipStream_t s) {
-  if constexpr (!std::is_same<T, bf16>::value) return 1;
+// there) instead of the register-staged 64x64 kernel. Same epilogue fields.
+static inline bool tall_rows_reroute(const GemmParams& p, int batch, int amode, int bmode, bool vec, PipeReroute& r) {
   if (batch != 1 || amode != A_ROW || bmode != B_NK || p.c_mode != C_ROW || p.ngroups > 0 || p.M <= 4096 ||
       p.N < 256 || p.K % 64 || p.lda != p.K || (p.a_so | p.a_si) != 0)
-    return 1;
-  GemmParams q = p;
-  q.H = q.Ho = p.M; q.W = q.Wo = 1; q.Cc = p.K; q.Rk = q.Sk = 1; q.sh = q.sw = 1; q.pt = q.pl = 0;
-  q.fd_HoWo = make_fastdiv(p.M); q.fd_Wo = make_fastdiv(1); q.fd_C = make_fastdiv(p.K); q.fd_S = make_fastdiv(1);
-  if (!pipe_eligible<bf16>(q, 1, A_IM2COL, B_NK, vec)) return 1;
-  if (q.M2 && pipe_split_for(q, 1) != 1) return 1;  // the M2 mask rides in the pipe epilogue only
-  log_gemm<bf16>(p, batch, amode, bmode, 170 + pipe_cfg(q, 1), pipe_split_logged(q, 1));
-  return launch_pipe_auto<A_IM2COL>(q, 1, s);
+    return false;
+  rows_as_image(r.q = p);
+  if (!pipe_eligible<bf16>(r.q, 1, A_IM2COL, B_NK, vec)) return false;
+  r.plan = pipe_plan(r.q, 1, A_IM2COL);
+  return !p.M2 || r.plan.splits == 1;  // the M2 mask rides in the pipe epilogue only
 }
 
+// CFG_SMALL: the skinny / split forms by launch_small; atomic C as one unsplit launch
 template <typename T>
-int dispatch_gemm_impl(GemmParams& p, int batch, int amode, int bmode, bool vec, hipStream_t s) {
-  if constexpr (std::is_same<T, bf16>::value) {
-    if (wg_job_eligible(p, batch, amode, bmode, vec)) {
-      log_gemm<T>(p, batch, amode, bmode, 150);
-      return defer_wg_jobs(p, batch, s);
-    }
+static int dispatch_small(GemmParams& p, int batch, int amode, int bmode, hipStream_t s) {
+  if (p.accumulate == 2) {  // atomic C: no split needed (and no workspace)
+    // one writer per element: a read-modify-write is the same sum on one
+    // stream, at a fraction of the per-element atomics' cost
+    if (batch == 1) p.accumulate = 1;
+    p.split_k = 1;
+    p.k_per_split = p.K;
+    p.ws_part = nullptr;
+    if (const int st = touch_c(p, batch, s)) return st;
+    log_gemm<T>(p, batch, amode, bmode, CFG_SMALL);
+    hipLaunchKernelGGL((gemm_small_kernel<T, 4>), dim3(cdiv(p.M, 32) * cdiv(p.N, 64), 1, batch), dim3(256), 0, s, p);
+    return check_launch("gemm_small_kernel");
   }
-  if constexpr (std::is_same<T, bf16>::value) {
-    if (p.c_mode == C_SCATTER) {
-      const int st = scatter_via_pipe(p, batch, amode, bmode, vec, s);
-      if (st != 1) return st;
-    }
-  }
-  if (p.M2) {
-    const int st = dispatch_with_m2<T>(p, batch, amode, bmode, vec, s);
-    if (st != 1) return st;
-  }
-  if constexpr (std::is_same<T, bf16>::value) {
-    if (pipe_eligible<T>(p, batch, amode, bmode, vec)) {
-      log_gemm<T>(p, batch, amode, bmode,
-                  130 + (amode == A_ROW ? (pipe_row_short(p, batch) ? row_short_cfg(p) : 3) : pipe_cfg(p, batch)),
-                  pipe_split_logged(p, batch));
-      return amode == A_IM2COL ? launch_pipe_auto<A_IM2COL>(p, batch, s) : launch_pipe_auto<A_ROW>(p, batch, s);
-    }
-    const int st = rows_via_im2col<T>(p, batch, amode, bmode, vec, s);
-    if (st != 1) return st;
-  }
-  if constexpr (std::is_same<T, bf16>::value) {
-    if (pipe_wg_eligible(p, batch, amode, bmode, vec)) {
-      g_wg_queued = false;
-      const int st = amode == A_IM2COL_T ? launch_pipe_wg<A_IM2COL_T>(p, s) : launch_pipe_wg<A_COL>(p, s);
-      log_gemm<T>(p, batch, amode, bmode, g_wg_queued ? 111 : 110);  // 111: queued for a grouped launch (cfg 112)
-      return st;
-    }
-  }
-  const int cfg = choose_cfg(amode, bmode, p.M, p.N, p.K, batch, p.accumulate, p.c_mode);
-  if (cfg == CFG_SMALL) {
-    if (p.accumulate == 2) {  // atomic C: no split needed (and no workspace)
-      // one writer per element: a read-modify-write is the same sum on one
-      // stream, at a fraction of the per-element atomics' cost
-      if (batch == 1) p.accumulate = 1;
-      p.split_k = 1;
-      p.k_per_split = p.K;
-      p.ws_part = nullptr;
-      {
-        const int st = touch_c(p, batch, s);
-        if (st) return st;
-      }
-      dim3 grid(cdiv(p.M, 32) * cdiv(p.N, 64), 1, batch);
-      log_gemm<T>(p, batch, amode, bmode, cfg);
-      hipLaunchKernelGGL((gemm_small_kernel<T, 4>), grid, dim3(256), 0, s, p);
-      return check_launch("gemm_small_kernel");
-    }
-    const int st = launch_small<T>(p, batch, s);
-    log_gemm<T>(p, batch, amode, bmode, cfg);
-    return st;
-  }
-  int BK = kCfg[cfg].bk;
-  if (cfg == CFG_128_128_64 && !(amode == A_IM2COL || amode == A_ROW || amode == A_IM2COL_T || amode == A_COL)) BK = 32;
-  if (cfg == CFG_64_64_64 && !(amode == A_IM2COL || amode == A_ROW || amode == A_IM2COL_T)) BK = 32;
-  BK = bk_of<T>(BK);
+  const int st = launch_small<T>(p, batch, s);
+  log_gemm<T>(p, batch, amode, bmode, CFG_SMALL);
+  return st;
+}
+
+// The register-staged family's split policy at tile config cfg, K-tile depth
+// BK: the split count of a split through the workspace (ws_split_for; p
+// untouched), else 1 with p.split_k / p.k_per_split set for the launch
+// (k-grouped and atomic-C launches split over grid.y, the rest run unsplit).
+static int staged_split(GemmParams& p, int batch, int cfg, int BK) {
   // split-K (only with fp32 atomic accumulation)
   if (p.ngroups > 0 && p.group_k) {
     // k-grouped: every group's reduction range is cut into splits of kt_per
     // K-tiles; grid.y enumerates the splits of all groups
-    long long tot_kt = 0;
-    for (int g = 0; g < p.ngroups; ++g) tot_kt += cdiv(p.groups[g].K, BK);
+    const long long tot_kt = k_tiles(p, BK);
     const long long blocks = blocks_for(p.M, p.N, batch, cfg);
     const long long want = (768 + blocks - 1) / blocks;
     int kt_per = (int)((tot_kt + want - 1) / want);
@@ -1068,45 +1017,28 @@ int dispatch_gemm_impl(GemmParams& p, int batch, int amode, int bmode, bool vec,
     if (p.split_k == 1 && (batch == 1 || c_batches_disjoint(p, batch))) p.accumulate = 1;
   } else {
     const int S = ws_split_for(p, batch, cfg, BK);
-    if (S > 1) {
-      // partial slabs (no epilogue) into the workspace, then sum + epilogue
-      GemmParams q = p;
-      const int nkt = cdiv(p.K, BK);
-      const int kt_per = cdiv(nkt, S);
-      q.split_k = cdiv(nkt, kt_per);
-      q.k_per_split = kt_per * BK;
-      q.bias = nullptr;
-      q.col_scale = nullptr;
-      q.R = nullptr;
-      q.act = FPNMT_ACT_NONE;
-      q.drop_p = 0.f;
-      q.drop_seed_dev = nullptr;
-      q.alpha = 1.f;
-      q.c_f32 = 1;
-      q.accumulate = 0;
-      q.C = g_split_ws.part;
-      q.ldc = p.N;
-      q.c_so = q.c_si = 0;
-      q.c_split = (long long)p.M * p.N;  // p.M = the groups' rows in total
-      RowOffsets ro{};
-      for (int g = 0, r = 0; g < p.ngroups; ++g) {  // groups' slab rows back to back
-        ro.off[g] = r;
-        q.groups[g].C = g_split_ws.part + (long long)r * p.N;
-        q.groups[g].R = nullptr;
-        r += p.groups[g].M;
-        ro.off[g + 1] = r;
-      }
-      log_gemm<T>(q, batch, amode, bmode, cfg);
-      int st = launch_modes<T>(cfg, q, batch, amode, bmode, vec, s);
-      if (st) return st;
-      const long long items = (long long)p.M * cdiv(p.N, 4);
-      hipLaunchKernelGGL((gemm_splitk_reduce_kernel<T>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, p,
-                         (const float*)g_split_ws.part, q.split_k, ro);
-      return check_launch("gemm_splitk_reduce_kernel");
-    }
+    if (S > 1) return S;
     p.split_k = 1;
     p.k_per_split = ((p.K + BK - 1) / BK) * BK;
     if (p.k_per_split == 0) p.k_per_split = BK;
+  }
+  return 1;
+}
+
+// the register-staged and small kernels: every launch no LDS-DMA route took
+template <typename T>
+static int dispatch_staged(GemmParams& p, int batch, int amode, int bmode, bool vec, hipStream_t s) {
+  const int cfg = choose_cfg(amode, bmode, p.M, p.N, p.K, batch, p.accumulate, p.c_mode);
+  if (cfg == CFG_SMALL) return dispatch_small<T>(p, batch, amode, bmode, s);
+  const int BK = staged_bk<T>(amode, cfg);
+  const int S = staged_split(p, batch, cfg, BK);
+  if (S > 1) {
+    // partial slabs (no epilogue) into the workspace, then sum + epilogue
+    const int nkt = cdiv(p.K, BK), kt_per = cdiv(nkt, S);
+    return launch_ws_split<T>(p, cdiv(nkt, kt_per), kt_per * BK, s, [&](GemmParams& q) {
+      log_gemm<T>(q, batch, amode, bmode, cfg);
+      return launch_modes<T>(cfg, q, batch, amode, bmode, vec, s);
+    });
   }
   if (p.accumulate == 2 && p.split_k > 1 && slab_fits(p, batch, p.split_k)) {
     // several adders per C element: partial slabs + ordered reduce
@@ -1116,12 +1048,64 @@ int dispatch_gemm_impl(GemmParams& p, int batch, int amode, int bmode, bool vec,
     const int st = launch_modes<T>(cfg, q, batch, amode, bmode, vec, s);
     return st ? st : launch_wgrad_reduce(p, batch, base, s);
   }
-  if (p.accumulate != 0 && p.c_f32) {
-    const int st = touch_c(p, batch, s);
-    if (st) return st;
-  }
+  if (p.accumulate != 0 && p.c_f32)
+    if (const int st = touch_c(p, batch, s)) return st;
   log_gemm<T>(p, batch, amode, bmode, cfg);
   return launch_modes<T>(cfg, p, batch, amode, bmode, vec, s);
+}
+
+// The routes in the order they are tried (the LDS-DMA ones: bf16 only). A
+// pipe route is planned once (PipePlan), logged and launched from the plan.
+template <typename T>
+int dispatch_gemm_impl(GemmParams& p, int batch, int amode, int bmode, bool vec, hipStream_t s) {
+  constexpr bool BF16 = std::is_same<T, bf16>::value;
+  if constexpr (BF16) {
+    // 1. Dense weight gradients in a deferred region: the job queue
+    if (wg_job_eligible(p, batch, amode, bmode, vec)) {
+      log_gemm<T>(p, batch, amode, bmode, ROUTE_DENSE_JOB);
+      return defer_wg_jobs(p, batch, s);
+    }
+    // 2. scattered rows: the pipe kernel into workspace rows + the scatter pass
+    PipeReroute r;
+    if (p.c_mode == C_SCATTER && scatter_reroute(p, batch, amode, bmode, vec, r)) {
+      log_gemm<T>(p, batch, amode, bmode, ROUTE_SCATTER_PIPE + r.plan.cfg, r.plan.splits);
+      return launch_scatter_reroute(p, r, s);
+    }
+  }
+  const bool piped = pipe_eligible<T>(p, batch, amode, bmode, vec);
+  const PipePlan plan = piped ? pipe_plan(p, batch, amode) : PipePlan{};
+  // 3. the M2 mask: in the epilogue of an unsplit pipe launch and of the
+  // register-staged kernel's scattered rows (strided 1x1 bwd-data: only its row
+  // epilogue applies M2 at the scattered row), else a pass of its own
+  if (p.M2) {
+    if (batch != 1 || p.accumulate == 2 || p.c_f32 || p.ngroups > 0)
+      return fail(FPNMT_E_UNSUPPORTED, "gemm: the M2 mask needs batch 1, bf16 C, no atomics");
+    if (p.c_mode != C_SCATTER && !(piped && plan.splits == 1))
+      return dispatch_m2_unfused<T>(p, batch, amode, bmode, vec, s);
+  }
+  if constexpr (BF16) {
+    // 4. the pipe kernel
+    if (piped) {
+      log_gemm<T>(p, batch, amode, bmode, ROUTE_PIPE + plan.cfg, plan.splits);
+      return amode == A_IM2COL ? launch_pipe_plan<A_IM2COL>(plan, p, batch, s)
+                               : launch_pipe_plan<A_ROW>(plan, p, batch, s);
+    }
+    // 5. tall rows: the conv pipe classes over a 1x1 implicit GEMM
+    PipeReroute r;
+    if (tall_rows_reroute(p, batch, amode, bmode, vec, r)) {
+      log_gemm<T>(p, batch, amode, bmode, ROUTE_TALL_ROWS + r.plan.cfg, r.plan.splits);
+      return launch_pipe_plan<A_IM2COL>(r.plan, r.q, 1, s);
+    }
+    // 6. the pipelined weight gradient
+    if (pipe_wg_eligible(p, batch, amode, bmode, vec)) {
+      bool queued = false;
+      const int st = amode == A_IM2COL_T ? launch_pipe_wg<A_IM2COL_T>(p, s, queued) : launch_pipe_wg<A_COL>(p, s, queued);
+      log_gemm<T>(p, batch, amode, bmode, queued ? ROUTE_PIPE_WG_QUEUED : ROUTE_PIPE_WG);
+      return st;
+    }
+  }
+  // 7. register-staged / small
+  return dispatch_staged<T>(p, batch, amode, bmode, vec, s);
 }
 
 }  // namespace fpnmt

@@ -148,6 +148,8 @@ PP = C.POINTER(C.c_void_p)  # a table of device pointers ((C.c_void_p * n)(...))
 SIGNATURES = {
     "fpnmt_version": [],
     "fpnmt_set_workspace": [P, LL],
+    "fpnmt_set_wide_cfg": [I],
+    "fpnmt_get_wide_cfg": [],
     "fpnmt_fill_zero": [P, LL, P],
     "fpnmt_fill_zero_grid": [P, LL, I, P],
     "fpnmt_defer_begin": [P, LL],

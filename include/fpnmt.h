@@ -84,6 +84,17 @@ int fpnmt_fill_zero_grid(void* p, long long bytes, int max_blocks, fpnmt_stream_
  * GEMMs using it must not run concurrently on different streams.          */
 int fpnmt_set_workspace(void* ws, long long bytes);
 
+/* Test / probe hook: the tile form of the wide bf16 conv classes, process-wide.
+ * 0 (the default): chosen per launch by tile count. 6: the 128-row M step in
+ * both classes (128x256 loader tile, cfg 6; 128x128 loader tile, cfg 7).
+ * 10: the 112-row M step on the 128x256 tile (cfg 10); the 128x128 class stays
+ * automatic. Every form computes the same bytes (tests/test_gpu_kernels.py:
+ * test_conv_wide_tiles_bitwise); only the tiling differs. Any other value:
+ * FPNMT_E_ARG, the setting unchanged. Callers reset it to 0 when done.
+ * fpnmt_get_wide_cfg: the current setting.                                  */
+int fpnmt_set_wide_cfg(int cfg);
+int fpnmt_get_wide_cfg(void);
+
 /* Deferred ordered reductions. Between fpnmt_defer_begin and
  * fpnmt_defer_flush, the ordered second passes of the fp32 gradient
  * reductions — split-K weight-gradient slabs -> dw (bwd-filter / transposed

@@ -96,7 +96,7 @@ class Case:
     mask: bool = False  # the M2 operand: out *= relu'(y)
     acc: int = 0  # 1: C += into bf16 C, 2: the fp32 weight-gradient accumulation
     c_f32: bool = False
-    wide: str = ""  # FPNMT_WIDE_CFG for the case
+    wide: str = ""  # fpnmt_set_wide_cfg for the case ("" = 0, automatic)
     # expected route details
     cmode: int = C_ROW
     psplit: int | None = None  # log psplit= (pipe routes; 1 = unsplit)
@@ -273,9 +273,11 @@ REACHABLE = (
 )
 # Codes the arithmetic of the dispatch rules excludes:
 #   134       launch_pipe_cfg case 4: no dispatch rule returns 4 (pipe_cfg gives
-#             0 1 2 6 7 8 10 11, row_short_cfg 5 8 9, tall A_ROW 3); it is
-#             instantiated for tools/fwd_bench.hip's "split cfg4" variants only
-#   160       cfg 0 needs a residual operand, which scatter_via_pipe refuses
+#             0 1 2 6 7 8 10 11, row_short_cfg 5 8 9, tall A_ROW 3); the
+#             library does not instantiate it (pipe_cfg_built: only the pairs
+#             a rule returns are compiled, anything else is FPNMT_E_UNSUPPORTED);
+#             tools/fwd_bench.hip builds it for its "split cfg4" variants
+#   160       cfg 0 needs a residual operand, which scatter_reroute refuses
 #   163-165, 169, 173-175, 179: cfg 3 / 5 / 9 are A_ROW-only, 4 as above
 #   176, 180  the wide class needs >= 192 tiles of 128x256 at K >= 1024, and
 #             the A_ROW pipe class (cfg 3) takes every such GEMM first
@@ -748,20 +750,20 @@ def child_main(outdir):
         except FileNotFoundError:
             return []
 
+    from fpnmt import _lib as L
     for case in CASES:
-        if case.wide:
-            os.environ["FPNMT_WIDE_CFG"] = case.wide
-        else:
-            os.environ.pop("FPNMT_WIDE_CFG", None)
         inp = inputs(case)
         outs, lines = [], []
-        for _ in range(2):
-            before = len(n_lines())
-            outs.append(run_gpu(case, inp))
-            lines.append(n_lines()[before:])
+        try:
+            L.call("fpnmt_set_wide_cfg", int(case.wide or 0))
+            for _ in range(2):
+                before = len(n_lines())
+                outs.append(run_gpu(case, inp))
+                lines.append(n_lines()[before:])
+        finally:
+            L.call("fpnmt_set_wide_cfg", 0)
         res[case.name] = {"out": outs[0].cpu(), "same": bool(torch.equal(outs[0], outs[1])), "log": lines}
         print(case.name, lines[0], flush=True)
-    os.environ.pop("FPNMT_WIDE_CFG", None)
     torch.save(res, os.path.join(outdir, "results.pt"))
 
 

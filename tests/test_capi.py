@@ -37,6 +37,27 @@ def test_version_and_error_path():
     assert rc == -1 and b"null" in L.lib.fpnmt_last_error()
 
 
+def test_wide_cfg_hook_validates():
+    """fpnmt_set_wide_cfg takes 0 / 6 / 10; anything else is FPNMT_E_ARG with
+    a message and leaves the setting as it was. No GPU call: the setting is
+    one process-wide int."""
+    from fpnmt import _lib as L
+    assert L.lib.fpnmt_get_wide_cfg() == 0  # the default: automatic
+    try:
+        for ok in (6, 10, 0, 10):
+            assert L.lib.fpnmt_set_wide_cfg(ok) == 0
+            assert L.lib.fpnmt_get_wide_cfg() == ok
+        for bad in (7, -1):
+            rc = L.lib.fpnmt_set_wide_cfg(bad)
+            assert rc == L.E_ARG
+            msg = L.lib.fpnmt_last_error()
+            assert b"set_wide_cfg" in msg and str(bad).encode() in msg
+            assert L.lib.fpnmt_get_wide_cfg() == 10  # unchanged by the refusal
+    finally:
+        assert L.lib.fpnmt_set_wide_cfg(0) == 0
+    assert L.lib.fpnmt_get_wide_cfg() == 0
+
+
 def test_struct_layouts_match_header():
     """ctypes mirrors of the descriptor structs have the C sizes."""
     from fpnmt import _lib as L

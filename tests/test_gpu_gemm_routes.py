@@ -36,7 +36,6 @@ CHILD_TIMEOUT_S = 420  # the table runs in ~1 min: imports, 3 GiB arena, ~60 cas
 def child(tmp_path_factory):
     out = tmp_path_factory.mktemp("gemm_routes")
     env = dict(os.environ, FPNMT_GEMM_LOG=str(out / "gemm.log"))
-    env.pop("FPNMT_WIDE_CFG", None)
     r = subprocess.run([sys.executable, os.path.abspath(G.__file__), str(out)], env=env, capture_output=True, text=True,
                        timeout=CHILD_TIMEOUT_S)
     if r.returncode != 0:

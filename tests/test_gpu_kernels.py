@@ -1209,31 +1209,35 @@ def test_conv_bias_grad_folded_into_wgrad(case, monkeypatch):
 
 
 @pytest.mark.parametrize("n,h", [(32, 28), (33, 28), (64, 28), (64, 14), (32, 14)])
-def test_conv_wide_tiles_bitwise(n, h, monkeypatch):
+def test_conv_wide_tiles_bitwise(n, h):
     """The wide conv class's two loader tiles (csrc/gemm_dispatch.h
-    wide_cfg, forced by FPNMT_WIDE_CFG: 128x256 cfg 6; the same image at a
+    wide_cfg, forced by fpnmt_set_wide_cfg: 128x256 cfg 6; the same image at a
     112-row M step, rows 112-127 fed the zero chunk, cfg 10) give the same K
     order per output element, so the forward,
     (14x14 at batch 64 / 32: the 128x128 loader class, cfg 7 against its
-    112-row M step cfg 11; FPNMT_WIDE_CFG=6 keeps the 128-row step there too)
+    112-row M step cfg 11; fpnmt_set_wide_cfg(6) keeps the 128-row step there too)
     the bwd-data (same class: K = 2304) and the weight gradient are bitwise
     equal; ragged M (33 images: partial last tiles) and batch 64 (two waves of
     blocks) included. The forward is also bounded against a torch CPU fp32 conv
     on the same bf16 operands (the output's bf16 rounding + 1e-2 absolute)."""
+    from fpnmt import _lib as L
     from fpnmt.layers import Conv2D
     torch.manual_seed(5)
     layer = Conv2D(256, 256, 3, padding="same", activation="relu", use_bias=True).to(DEV)
     x0 = (torch.rand(n, h, h, 256, device=DEV) * 2 - 1).to(torch.bfloat16)
     g = (torch.randn(n, h, h, 256, device=DEV) * 0.1).to(torch.bfloat16)
     outs = {}
-    for cfg in ("6", "10"):
-        monkeypatch.setenv("FPNMT_WIDE_CFG", cfg)
-        layer.kernel.grad = None
-        x = x0.clone().requires_grad_(True)
-        y = layer(x)
-        y.backward(g)
-        torch.cuda.synchronize()
-        outs[cfg] = (y.detach().clone(), x.grad.clone(), layer.kernel.grad.clone())
+    try:
+        for cfg in ("6", "10"):
+            L.call("fpnmt_set_wide_cfg", int(cfg))
+            layer.kernel.grad = None
+            x = x0.clone().requires_grad_(True)
+            y = layer(x)
+            y.backward(g)
+            torch.cuda.synchronize()
+            outs[cfg] = (y.detach().clone(), x.grad.clone(), layer.kernel.grad.clone())
+    finally:
+        L.call("fpnmt_set_wide_cfg", 0)
     for a, b in zip(outs["6"], outs["10"]):
         assert torch.equal(a, b)
     xr = x0.float().cpu().permute(0, 3, 1, 2)
