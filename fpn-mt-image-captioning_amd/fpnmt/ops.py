@@ -2142,6 +2142,83 @@ class MaskedXentFn(torch.autograd.Function):
         return dlog.reshape(ctx.shape), None
 
 
+class WeightedXentFn(torch.autograd.Function):
+    """The self-critical loss: MaskedXentFn with row r weighted by
+    w[r // w_div] (a sampled caption's advantage; w_div = the rows per
+    caption), still a mean over ALL rows (fpnmt_xent_weighted_fwd_bwd).
+    w is read on the device at execution, so a replayed graph sees the
+    weights copied into it since. The gradient is computed in the same launch
+    (saved) — the loss must be the root of backward; w gets no gradient.
+    With_logp: also returns row_logp (rows,), the log-probability of every
+    label under the model (0 at a pad), not differentiable."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, w, w_div, with_logp=False):
+        v = logits.shape[-1]
+        lg = logits.reshape(-1, v)
+        if lg.dtype != torch.float32 or w.dtype != torch.float32:
+            raise TypeError("WeightedXentFn expects fp32 logits and fp32 weights")
+        lg = lg.contiguous()
+        lab = labels.reshape(-1).to(torch.int32).contiguous()
+        w = w.contiguous()
+        rows = lg.shape[0]
+        if w_div < 1 or rows % w_div or w.numel() * w_div != rows:
+            raise ValueError(f"WeightedXentFn: {rows} rows need {rows} / w_div weights, got {w.numel()} "
+                             f"(w_div {w_div})")
+        loss = torch.empty((1,), dtype=torch.float32, device=lg.device)
+        need = ctx.needs_input_grad[0]
+        dlog = torch.empty_like(lg) if need else None
+        logp = _empty((rows,), torch.float32, lg.device) if with_logp else None
+        call("fpnmt_xent_weighted_fwd_bwd", L.F32, rows, v, ptr(lg), v, ptr(lab), ptr(w), int(w_div), ptr(loss),
+             ptr(logp), ptr(dlog), v, 1.0, stream_ptr())
+        if need:
+            ctx.save_for_backward(dlog)
+        ctx.shape = logits.shape
+        if with_logp:
+            ctx.mark_non_differentiable(logp)
+            return loss.reshape(()), logp
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        (dlog,) = ctx.saved_tensors
+        return dlog.reshape(ctx.shape), None, None, None, None
+
+
+class RepeatRowsFn(torch.autograd.Function):
+    """y[i * n + s] = x[i] for s < n (torch.repeat_interleave(x, n, 0)): the
+    encoder output of B images as the B * n rows the decoder trains n
+    sampled captions per image on. The backward sums every image's n row
+    gradients in fp32 in ascending s and rounds once (fpnmt_rowsum_groups,
+    no atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, n):
+        x = x.contiguous()
+        b = x.shape[0]
+        ln = x.numel() // b if b else 0
+        y = _empty((b * n,) + tuple(x.shape[1:]), x.dtype, x.device)
+        call("fpnmt_repeat_rows", dtype_code(x.dtype), b, n, ln, ptr(x), ptr(y), stream_ptr())
+        ctx.n = n
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        import ctypes
+        n = ctx.n
+        dy = dy.contiguous()
+        b = dy.shape[0] // n
+        ln = dy.numel() // (b * n) if b * n else 0
+        acc = _empty((b,) + tuple(dy.shape[1:]), torch.float32, dy.device)
+        dx = acc if dy.dtype == torch.float32 else torch.empty_like(acc, dtype=dy.dtype)
+        if ln >= 1 << 31:
+            raise ValueError("RepeatRowsFn: more than 2^31 - 1 elements per image")
+        tab = (ctypes.c_void_p * 1)(dy.data_ptr())
+        call("fpnmt_rowsum_groups", dtype_code(dy.dtype), 1, b, n, ln, tab, ptr(acc), ptr(dx) if dx is not acc else None,
+             None, 0, 0, stream_ptr())
+        return dx, None
+
+
 # ------------------------------------------------------------ elementwise
 class DropoutFn(torch.autograd.Function):
     @staticmethod

@@ -14,6 +14,14 @@ the second call captures the whole step into a hipGraph (torch.cuda.CUDAGraph
 drives hipGraph on ROCm) and every later call only copies the new batch into
 the static input buffers and replays.
 
+step_weighted(img, tok, weights) is the self-critical form of the same step
+(not in the reference): tok holds n = tok.shape[0] // B captions per image,
+the encoder runs once per image and its output is repeated n times for the
+decoder (ops.RepeatRowsFn), and caption r's CE terms are weighted by
+weights[r] (ops.WeightedXentFn, still a mean over all rows). Its graphs are
+captured per shape beside the plain step's; arena, optimizer state and step
+counter are shared, so the two kinds of step can alternate.
+
 With world > 1 (or split_backward=True) the step is a sequence of graphs:
   G1      forward + loss + the decoder's backward (stops at the encoder
           output, which enters the decoder as a leaf)
@@ -134,6 +142,7 @@ class TrainEngine:
         self.calls = 0
         self.graphs = None
         self.static = None
+        self._wsteps = {}  # step_weighted: shapes -> [calls, graphs, static]
 
     # ------------------------------------------------------------ pieces
     def _one(self, loss):
@@ -167,7 +176,21 @@ class TrainEngine:
         if zs is not None:
             torch.cuda.current_stream().wait_stream(zs)
 
-    def _fwd_bwd(self, img, tok):
+    def _logits_loss(self, enc_fn, tok, weights):
+        """targets -> encoder output (enc_fn) -> decoder -> logits -> loss.
+        weights None: the plain step's masked CE. Otherwise tok holds
+        n = rows / images captions per image: the encoder output is repeated n
+        times and caption r's terms are weighted by weights[r]."""
+        m = self.model
+        tar_inp, tar_real, mask = ops.decoder_targets(tok)  # tok[:, :-1], tok[:, 1:], create_masks(tar_inp)
+        enc = enc_fn()
+        if weights is None:
+            dec, _ = m.decoder(tar_inp, enc, True, mask, None)
+            return ops.MaskedXentFn.apply(m.final_layer(dec), tar_real)
+        dec, _ = m.decoder(tar_inp, ops.RepeatRowsFn.apply(enc, tok.shape[0] // enc.shape[0]), True, mask, None)
+        return ops.WeightedXentFn.apply(m.final_layer(dec), tar_real, weights, tok.shape[1] - 1)
+
+    def _fwd_bwd(self, img, tok, weights=None):
         ops.runtime.reset_sites()  # dropout sites numbered from the step's start
         ops.reset_grad_sums()
         zs = self._zero_grad_fork()
@@ -175,9 +198,7 @@ class TrainEngine:
                  and 0 < self.early_blocks < self.arena.nblocks)
         ops.runtime.on_transformer_grads = self._early_update if early else None
         try:
-            tar_inp, tar_real, mask = ops.decoder_targets(tok)  # tok[:, :-1], tok[:, 1:], create_masks(tar_inp)
-            logits, _ = self.model(img, tar_inp, True, mask)
-            loss = ops.MaskedXentFn.apply(logits, tar_real)
+            loss = self._logits_loss(lambda: self.model.encoder(img, True, None), tok, weights)
             self._zero_grad_join(zs)
             with L.deferred_reductions(fpnmt.config.defer_reductions), ops.side_wgrad():
                 torch.autograd.backward([loss], [self._one(loss)])  # ordered reductions batched at the exit
@@ -210,21 +231,24 @@ class TrainEngine:
                                     max_grid=fpnmt.config.early_update_grid, **self.adam)
         self._early_pending = True
 
-    def _fwd_bwd_split(self, img, tok):
+    def _fwd_bwd_split(self, img, tok, weights=None):
         """G1: forward + loss + the decoder's backward down to the encoder
-        output (a leaf of the decoder)."""
+        output (a leaf of the decoder; with weights, the leaf is the encoder
+        output per image, ahead of its repeat)."""
         ops.runtime.reset_sites()
         ops.reset_grad_sums()
         zs = self._zero_grad_fork()
         m = self.model
-        tar_inp, tar_real, mask = ops.decoder_targets(tok)
-        feats, stages = m.encoder.feature_extractor.staged(img, training=True)
-        leaves = [f.detach().requires_grad_(f.requires_grad) for f in feats]
-        enc = m.encoder.from_features(leaves, True, None)
-        enc_leaf = enc.detach().requires_grad_(True)
-        dec, _ = m.decoder(tar_inp, enc_leaf, True, mask, None)
-        logits = m.final_layer(dec)
-        loss = ops.MaskedXentFn.apply(logits, tar_real)
+        side = {}
+
+        def encode():
+            feats, stages = m.encoder.feature_extractor.staged(img, training=True)
+            leaves = [f.detach().requires_grad_(f.requires_grad) for f in feats]
+            enc = m.encoder.from_features(leaves, True, None)
+            side.update(stages=stages, leaves=leaves, enc=enc, enc_leaf=enc.detach().requires_grad_(True))
+            return side["enc_leaf"]
+        loss = self._logits_loss(encode, tok, weights)
+        stages, leaves, enc, enc_leaf = side["stages"], side["leaves"], side["enc"], side["enc_leaf"]
         self._zero_grad_join(zs)
         with L.deferred_reductions(fpnmt.config.defer_reductions), ops.side_wgrad():
             torch.autograd.backward([loss], [self._one(loss)])
@@ -300,9 +324,9 @@ class TrainEngine:
         if fp:
             fp.mark_fresh()
 
-    def _eager(self, img, tok):
+    def _eager(self, img, tok, weights=None):
         if self.split:
-            loss = self._fwd_bwd_split(img, tok)
+            loss = self._fwd_bwd_split(img, tok, weights)
             works = self._exchange(0, wait=False)
             self._bwd_encoder()
             works += self._exchange(1, wait=False)
@@ -312,7 +336,7 @@ class TrainEngine:
             for w in works:
                 w.wait()
         else:
-            loss = self._fwd_bwd(img, tok)
+            loss = self._fwd_bwd(img, tok, weights)
             self._exchange()
         self._update()
         return loss.detach()
@@ -353,8 +377,41 @@ class TrainEngine:
             return self._eager(img, tok)
         self.static[0].copy_(img)
         self.static[1].copy_(tok)
+        return self._replay(self.graphs, self.static[2])
+
+    def step_weighted(self, img, tok, weights):
+        """One self-critical step: img (B, H, W, 3), tok (B * n, T_full) padded
+        captions, n per image in image order, weights (B * n,) fp32 (the
+        captions' advantages; any sign). The step is step()'s with the encoder
+        run once per image and its output repeated n times, and the loss
+        (1 / rows) * sum_r weights[r // (T_full - 1)] * mask_r * ce_r. Returns
+        the (device) loss. The first call at a shape runs eagerly, the second
+        captures, later ones copy image, tokens and weights into the static
+        buffers and replay."""
+        B = img.shape[0]
+        if tok.dim() != 2 or B < 1 or tok.shape[0] % B or tok.shape[0] == 0:
+            raise ValueError(f"step_weighted: {tuple(tok.shape)} captions for {B} images")
+        if tuple(weights.shape) != (tok.shape[0],) or weights.dtype != torch.float32:
+            raise ValueError(f"step_weighted: weights must be fp32 of shape ({tok.shape[0]},), "
+                             f"got {weights.dtype} {tuple(weights.shape)}")
+        key = (tuple(img.shape), tuple(tok.shape), tok.dtype)
+        ent = self._wsteps.setdefault(key, [0, None, None])
+        ent[0] += 1
+        if not self.use_graph or ent[0] == 1:
+            flayers.prepare_all(self.model, fpnmt.compute_dtype())
+            return self._eager(img, tok, weights)
+        if ent[1] is None:
+            ent[1], ent[2] = self._capture(img, tok, weights)
+        graphs, static = ent[1], ent[2]
+        static[0].copy_(img)
+        static[1].copy_(tok)
+        static[3].copy_(weights)
+        return self._replay(graphs, static[2])
+
+    def _replay(self, graphs, loss):
+        """Replay one captured step (the exchanges between its graphs)."""
         if self.split:
-            g1, g2, *gs, g3 = self.graphs
+            g1, g2, *gs, g3 = graphs
             tl = _Timeline() if self._tl is not None else None
             g1.replay()
             works = self._exchange(0, wait=False)  # overlaps the next graphs on RCCL's stream
@@ -382,34 +439,41 @@ class TrainEngine:
             if tl:
                 tl.graph("G3")
                 self._tl.append(tl)
-            return self.static[2]
-        g_fb, g_up = self.graphs
+            return loss
+        g_fb, g_up = graphs
         g_fb.replay()
         if g_up is not None:
             self._exchange()
             g_up.replay()
-        return self.static[2]
+        return loss
 
-    def _capture(self, img, tok):
+    def _capture(self, img, tok, weights=None):
+        """Capture the step on static copies of its inputs. The plain step's
+        graphs become self.graphs / self.static; a weighted step's (graphs,
+        static) are returned to step_weighted."""
         s_img = img.detach().clone()
         s_tok = tok.detach().clone()
+        s_w = weights.detach().clone() if weights is not None else None
         out = {}
         if self.split:
             def g1():
-                out["loss"] = self._fwd_bwd_split(s_img, s_tok).detach()
+                out["loss"] = self._fwd_bwd_split(s_img, s_tok, s_w).detach()
             n = len(self.model.encoder.feature_extractor.stage_prefixes())
             stage_fns = [(lambda i=i: self._bwd_stage(i)) for i in range(n)]
-            self.graphs = capture_sequence([g1, self._bwd_encoder] + stage_fns + [self._update])
+            graphs = capture_sequence([g1, self._bwd_encoder] + stage_fns + [self._update])
         elif self.world == 1:
             def g():
-                out["loss"] = self._fwd_bwd(s_img, s_tok).detach()
+                out["loss"] = self._fwd_bwd(s_img, s_tok, s_w).detach()
                 self._update()
-            self.graphs = (capture_sequence([g])[0], None)
+            graphs = (capture_sequence([g])[0], None)
         else:
             def g1():
-                out["loss"] = self._fwd_bwd(s_img, s_tok).detach()
-            self.graphs = tuple(capture_sequence([g1, self._update]))
-        self.static = (s_img, s_tok, out["loss"])
+                out["loss"] = self._fwd_bwd(s_img, s_tok, s_w).detach()
+            graphs = tuple(capture_sequence([g1, self._update]))
+        static = (s_img, s_tok, out["loss"], s_w)
+        if weights is None:
+            self.graphs, self.static = graphs, static
+        return graphs, static
 
 
 class _Timeline:

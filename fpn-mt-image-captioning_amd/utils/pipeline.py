@@ -111,6 +111,38 @@ class Pipeline:
         self.train_loss(loss)
         return loss
 
+    def train_step_scst(self, img, refs, n_samples=5, baseline="mean", reward=None, temperature=1.0, top_k=0,
+                        top_p=1.0, seed=None):
+        """One self-critical (reward-optimising) step, the usual second phase
+        after cross-entropy training; not in the reference. Samples n_samples
+        captions per image (fpnmt.decode.SampleDecoder, max_seq_len - 1
+        positions), scores each on the host, and takes one optimizer step on
+        the samples weighted by their advantages (fpnmt.scst,
+        TrainEngine.step_weighted: the encoder runs once per image).
+
+        img (B, H, W, 3) on the GPU; refs: per image its reference captions as
+        token-id lists (without <start> / <end>). reward: None scores with
+        CIDEr-D over refs (utils.cider_reward.CiderDReward, document
+        frequencies of this batch), or any callable (image_index,
+        candidate_ids) -> float — e.g. a CiderDReward built once over the
+        whole training set, behind a lambda that maps the batch index to its
+        image key. baseline "mean": each sample against the mean reward of the
+        image's other samples (n_samples >= 2); "greedy": against the reward
+        of the greedy caption (one more decode). seed None: a new draw every
+        call; a given seed repeats its samples.
+
+        Returns {"loss" (device tensor), "reward_mean", "baseline_mean",
+        "sample_logp_mean", "samples", "advantages"}. The rewards are computed
+        on the host from the sampled ids, which costs the step one host
+        synchronisation; train_step has none."""
+        tr = getattr(self, "_scst", None)
+        if tr is None:
+            from fpnmt.scst import SelfCriticalTrainer
+            tr = self._scst = SelfCriticalTrainer(self.transformer, self.engine, self.start_token, self.end_token,
+                                                  self.max_seq_len)
+        return tr.step(img, refs, n_samples=n_samples, baseline=baseline, reward=reward, temperature=temperature,
+                       top_k=top_k, top_p=top_p, seed=seed)
+
     # ------------------------------------------------------------ predict
     @torch.no_grad()
     def predict(self, img, max_seq_len, plot_layer=False):

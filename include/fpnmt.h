@@ -610,6 +610,38 @@ int fpnmt_xent_fwd_bwd(int dtype, long long rows, int v, const float* logits, lo
                        const int32_t* labels, float* loss, void* dlogits, long long ldd,
                        float dloss_scale, fpnmt_stream_t stream);
 
+/* ---- advantage-weighted masked cross-entropy (self-critical training) ---
+ * The loss of a step whose caption rows carry a weight each (a sampled
+ * caption's advantage): row r weighs w[r / w_div] (device memory, read at
+ * execution: a replayed graph sees new weights once they are copied in;
+ * w_div = the rows per caption), mask_r = (labels[r] != 0);
+ *   loss         = (1 / rows) * sum_r w[r / w_div] * mask_r * ce_r
+ *                  (a mean over ALL rows, fpnmt_xent_fwd_bwd's convention;
+ *                  scalar, overwritten; summed in row order through the
+ *                  workspace: bitwise repeatable),
+ *   dlogits[r,j] = dloss_scale * w[r / w_div] * mask_r / rows * (softmax_j - [j == label_r])
+ *                  (may be NULL: loss and row_logp only; exact zeros for a
+ *                  pad row and for a zero weight),
+ *   row_logp[r]  = logits[r, label_r] - logsumexp(logits[r, :]), 0 for a pad
+ *                  row (may be NULL): the log-probability the decode paths sum.
+ * Weights may be negative or zero. A label outside [0, v) is never
+ * dereferenced and counts as a pad. Each row is read once (16-B loads where
+ * the row starts are 16-B aligned, i.e. ld % 4 == 0 on an aligned base) and
+ * held in registers up to v = 10 240; wider rows are read twice.
+ * FPNMT_E_ARG: a null pointer (but row_logp / dlogits), w_div < 1,
+ * rows % w_div != 0, ld < v, no workspace attached.                       */
+int fpnmt_xent_weighted_fwd_bwd(int dtype, long long rows, int v, const float* logits, long long ld,
+                                const int32_t* labels, const float* w, int w_div, float* loss, float* row_logp,
+                                void* dlogits, long long ldd, float dloss_scale, fpnmt_stream_t stream);
+
+/* ---- n caption rows per image: y[i * n + s, :] = x[i, :] for s < n -------
+ * x (b, len), y (b * n, len), len elements of dtype per image (the encoder
+ * output's S * d): the encoder runs once per image and the decoder on b * n
+ * rows. 16-B copies when len * sizeof(dtype) and both pointers allow. The
+ * backward, dx[i] = sum_s dy[i * n + s] in fp32 in ascending s, rounded once,
+ * is fpnmt_rowsum_groups(dtype, 1, b, n, len, {dy}, dx_f32, dx, ...).        */
+int fpnmt_repeat_rows(int dtype, int b, int n, long long len, const void* x, void* y, fpnmt_stream_t stream);
+
 /* ---- optimizer: Keras Adam(amsgrad) + per-tensor clip_by_norm ----------
  * Tensors are segments [off[i], off[i+1]) of flat fp32 arrays, processed in
  * blocks of block_elems that never cross a segment: block b covers
