@@ -220,6 +220,8 @@ SIGNATURES = {
     "fpnmt_beam_finalize": [I, I, P, I, P, P, P, F, P, I, P, P, P],
     "fpnmt_sample_step": [I, I, P, LL, F, I, F, ULL, P, P, P, P, P, I, I, I, P, P, P],
     "fpnmt_sample_uniform": [I, I, ULL, P, P, P],
+    "fpnmt_ciderd_reward": [P, I, I, P, I, P, P, P, P, P],  # fpnmt_cider_tables*: fpnmt.cider_device.CiderTables
+    "fpnmt_scst_pack": [I, I, I, P, P, P, I, P, P, P, I, I, I, P, I, P, P, P],
     "fpnmt_bn_stats": [I, LL, I, P, P, P, P, P, F, P],
     "fpnmt_bn_apply": [I, LL, I, P, P, P, P, P, F, I, P, P, P],
     "fpnmt_bn_bwd": [I, LL, I, P, P, P, P, F, I, P, P, P, P, P, P],
@@ -269,6 +271,8 @@ lib = _load()
 
 E_ARG, E_UNSUPPORTED, E_HIP = -1, -2, -3  # include/fpnmt.h status codes
 SAMPLE_FILTER_MAX_VOCAB = 16384  # FPNMT_SAMPLE_FILTER_MAX_VOCAB
+CIDER_MAX_LEN = 128  # FPNMT_CIDER_MAX_LEN
+SCST_MEAN, SCST_GREEDY = 0, 1  # FPNMT_SCST_*
 
 
 def check(status: int, what: str = ""):

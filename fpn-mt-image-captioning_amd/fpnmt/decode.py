@@ -377,3 +377,38 @@ class SampleDecoder(_CachedDecoder):
             rows = range(i * self.n_samples, (i + 1) * self.n_samples)
             out.append([(hist[r][1:1 + lens[r] - fin[r]], score[r]) for r in rows])
         return out
+
+    @torch.no_grad()
+    def decode_device(self, images, seed=None, check_every=0):
+        """decode() without the read-back: prepares and replays the same
+        positions with the same draws, and returns the decoder's OWN state
+        tensors (hist (R, T + 1) int32, slen, fin (R,) int32, score (R,)
+        fp32), valid until the next decode of this decoder. Row r's caption
+        is hist[r][1 : 1 + slen[r] - fin[r]] (sampled_ids turns the state
+        into lists). check_every 0 (the default) runs all positions and polls
+        nothing, so the call never waits for the device; a positive value
+        keeps decode()'s 4-byte fin.all() poll every that many positions for
+        callers who prefer the early exit."""
+        if images.shape[0] != self.n_images:
+            raise ValueError(f"expected {self.n_images} images, got {images.shape[0]}")
+        if seed is None:
+            seed = self._calls
+        self._calls += 1
+        self._prepare(images)
+        self.seed_dev.fill_(int(seed) & 0x7FFFFFFFFFFFFFFF)
+        for t in range(self.T):
+            if self.graphs is not None:
+                self.graphs[t].replay()
+            else:
+                self._step(t)
+            if check_every and (t + 1) % check_every == 0 and t + 1 < self.T and bool(self.fin.all()):
+                break
+        return self.hist, self.slen, self.fin, self.score
+
+
+def sampled_ids(hist, slen, fin):
+    """The state SampleDecoder.decode_device returns -> one token-id list per
+    row (without <start> and a final <end>), what decode() returns as ids.
+    Reads the three tensors back (one synchronisation)."""
+    h, n, f = hist.tolist(), slen.tolist(), fin.tolist()
+    return [h[r][1:1 + n[r] - f[r]] for r in range(len(n))]

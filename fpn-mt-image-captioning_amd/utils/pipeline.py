@@ -112,7 +112,7 @@ class Pipeline:
         return loss
 
     def train_step_scst(self, img, refs, n_samples=5, baseline="mean", reward=None, temperature=1.0, top_k=0,
-                        top_p=1.0, seed=None):
+                        top_p=1.0, seed=None, image_keys=None):
         """One self-critical (reward-optimising) step, the usual second phase
         after cross-entropy training; not in the reference. Samples n_samples
         captions per image (fpnmt.decode.SampleDecoder, max_seq_len - 1
@@ -134,14 +134,28 @@ class Pipeline:
         Returns {"loss" (device tensor), "reward_mean", "baseline_mean",
         "sample_logp_mean", "samples", "advantages"}. The rewards are computed
         on the host from the sampled ids, which costs the step one host
-        synchronisation; train_step has none."""
+        synchronisation; train_step has none.
+
+        reward a fpnmt.cider_device.DeviceCiderD (built once over the whole
+        training set, on the images' device): the rewards, advantages and
+        token rows are computed on the device (fpnmt_ciderd_reward,
+        fpnmt_scst_pack) and the step has no read-back and, from its third
+        call at a shape on, no host synchronisation. image_keys names the
+        images' keys in that corpus (None: the table rows 0 .. B - 1); refs
+        is not needed. Returns device tensors only: "loss", "rewards" (B, n)
+        f64, "advantages" (B, n) fp32, 0-dim "reward_mean" / "baseline_mean" /
+        "sample_logp_mean", and the sampler's "hist" / "slen" / "fin"
+        (fpnmt.decode.sampled_ids turns them into id lists); no "samples".
+        reward "device" builds such tables from this batch's refs every step
+        (the document frequencies of reward None): a convenience, with host
+        work for the tables; a corpus-level instance is the intended use."""
         tr = getattr(self, "_scst", None)
         if tr is None:
             from fpnmt.scst import SelfCriticalTrainer
             tr = self._scst = SelfCriticalTrainer(self.transformer, self.engine, self.start_token, self.end_token,
                                                   self.max_seq_len)
         return tr.step(img, refs, n_samples=n_samples, baseline=baseline, reward=reward, temperature=temperature,
-                       top_k=top_k, top_p=top_p, seed=seed)
+                       top_k=top_k, top_p=top_p, seed=seed, image_keys=image_keys)
 
     # ------------------------------------------------------------ predict
     @torch.no_grad()

@@ -22,6 +22,7 @@
  *   fpnmt_beam_step        softmax + top_k + gather + argmax of predict   utils/pipeline.py:115-147
  *   fpnmt_beam_step_log, fpnmt_beam_finalize   beam search proper (log-prob beams, n-best)   not in the reference
  *   fpnmt_sample_step, fpnmt_sample_uniform    sampled decoding (temperature, top-k, top-p)    not in the reference
+ *   fpnmt_ciderd_reward, fpnmt_scst_pack       CIDEr-D reward and advantages on the device     not in the reference
  *
  * Conventions (all functions):
  *   - Return 0 on success or a negative FPNMT_E* code; never throw across the ABI.
@@ -818,6 +819,72 @@ int fpnmt_sample_step(int rows, int vocab, const float* logits, long long ldl, f
                       int32_t* kept_out /* may be NULL */, fpnmt_stream_t stream);
 int fpnmt_sample_uniform(int rows, int t, unsigned long long seed, const long long* seed_dev, float* u_out,
                          fpnmt_stream_t stream);
+
+/* Device-side CIDEr-D reward (not in the reference; csrc/cider.hip): the
+ * arithmetic of utils/cider_reward.py CiderDReward (n = 4, clipped counts,
+ * Gaussian length penalty, x 10) on the sampler's device state, against
+ * reference tables packed once on the host (fpnmt/cider_device.py). All
+ * table pointers are device memory.
+ *   key      a k-gram (k <= 4) as one uint64: sum_i (tok_i + 1) << (16 i);
+ *            exact for 0 <= tok <= 65533.
+ *   df_keys  [n_df] ascending, unique; df_idf[n_df] = log(N) - log(max(1,
+ *            df)); a key absent from df_keys has idf idf_absent (= log N).
+ *   img_off  [n_images + 1]: image i's references are j in [img_off[i],
+ *            img_off[i + 1]); ref_off[R + 1]: reference j's entries are e in
+ *            [ref_off[j], ref_off[j + 1]), ref_keys ascending inside;
+ *            ref_w[e] = tf * idf; ref_norm[j][4] per order; ref_len[j] = the
+ *            sum of its bigram counts.
+ *   gauss    [n_gauss], gauss[d] the length factor at |len_h - len_r| = d
+ *            (an index past the table reads its last entry).
+ *   max_len  the longest candidate served, <= FPNMT_CIDER_MAX_LEN.
+ * fpnmt_ciderd_reward: reward[r] (fp64), r < rows, = the CIDEr-D of the
+ *   candidate hist[r][1 : 1 + slen[r] - fin[r]] (what the sampler drew,
+ *   without <start> and a final <end>; the length is clamped to [0, hist_ld -
+ *   1]) against the references of image img_index[r / n]. rows % n == 0. A
+ *   candidate of length 0 scores exactly 0; an img_index outside [0,
+ *   n_images) gives reward 0 with no table read. fp64, fixed-order sums, no
+ *   atomics: bitwise repeatable, and a row's value does not depend on the
+ *   other rows of the launch. hist_ld - 1 > max_len, or max_len >
+ *   FPNMT_CIDER_MAX_LEN: FPNMT_E_UNSUPPORTED.
+ * fpnmt_scst_pack: per image i < b, from reward[b * n] (fp64):
+ *   adv[i * n + s] (fp32) = reward - baseline, computed in fp64 and rounded
+ *     once; mode FPNMT_SCST_MEAN (n >= 2): the baseline of sample s is
+ *     (sum over s' != s, ascending, of reward[i * n + s']) / (n - 1); mode
+ *     FPNMT_SCST_GREEDY: greedy[i] (fp64[b]).
+ *   tok[i * n + s][width] (int64) = fpnmt.scst.pack_tokens' row: start_token,
+ *     the candidate's ids, end_token iff the candidate is shorter than
+ *     max_tokens (the positions the sampler ran: iff the row finished), zeros;
+ *     cut at width.
+ *   scalars[0..2] (fp64) = the means over all b * n rows of reward, baseline
+ *     and score (the sampler's fp32 log-probabilities), each summed by one
+ *     wave in a fixed order (lane-strided partials, a shuffle tree).
+ * Both: no allocation, no synchronisation, capturable.                     */
+#define FPNMT_CIDER_MAX_LEN 128
+#define FPNMT_SCST_MEAN 0
+#define FPNMT_SCST_GREEDY 1
+typedef struct fpnmt_cider_tables {
+  const unsigned long long* df_keys;
+  const double* df_idf;
+  long long n_df;
+  double idf_absent;
+  const int32_t* img_off;
+  int n_images;
+  int max_len;
+  const long long* ref_off;
+  const unsigned long long* ref_keys;
+  const double* ref_w;
+  const double* ref_norm;
+  const int32_t* ref_len;
+  const double* gauss;
+  int n_gauss;
+} fpnmt_cider_tables;
+int fpnmt_ciderd_reward(const fpnmt_cider_tables* t, int rows, int n, const int32_t* hist, int hist_ld,
+                        const int32_t* slen, const int32_t* fin, const int32_t* img_index, double* reward,
+                        fpnmt_stream_t stream);
+int fpnmt_scst_pack(int b, int n, int mode, const double* reward, const double* greedy /* may be NULL (mean) */,
+                    const int32_t* hist, int hist_ld, const int32_t* slen, const int32_t* fin, const float* score,
+                    int start_token, int end_token, int max_tokens, long long* tok, int width, float* adv,
+                    double* scalars, fpnmt_stream_t stream);
 
 /* ---- MobileNetV2 backbone (models/mobilenet.py:43-72 ->
  * keras MobileNetV2(alpha=1.0), models/retinanet.py:274) -------------------

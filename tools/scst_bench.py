@@ -11,6 +11,10 @@
   xent:   (f) fpnmt_xent_fwd_bwd and fpnmt_xent_weighted_fwd_bwd alone at
           4 960 rows x V 10 000, each as one captured graph of `--launches`
           launches, alternating windows, in the same process.
+  reward: (g) fpnmt_ciderd_reward and fpnmt_scst_pack alone at 160 rows x 31
+          positions, 5 references per image, measured like (f).
+  scst:   (h) the whole self-critical step end to end, the host-reward path
+          against the device-reward path in the same run, alternating calls.
 
 Expectations the numbers confirm or refute: (b) - (a) is the decoder side at
 5 x the rows, so (b) is far below (c); in (f) the new kernel takes no longer
@@ -189,9 +193,118 @@ def xent_bench(rows, V, w_div, launches, replays, rounds):
     print(json.dumps(out), flush=True)
 
 
+def _refs(B, V, seed):
+    g = torch.Generator().manual_seed(seed)
+    return [[torch.randint(4, V // 50, (int(torch.randint(8, 14, (1,), generator=g)),), generator=g).tolist()
+             for _ in range(5)] for _ in range(B)]
+
+
+def reward_bench(B, n, T, V, launches, replays, rounds):
+    """(g) fpnmt_ciderd_reward and fpnmt_scst_pack alone: B * n rows of T - 1
+    positions as a sampler leaves them (lengths 8 .. T - 1, tokens from the
+    references' vocabulary), 5 references per image."""
+    from fpnmt import _lib as L
+    from fpnmt.cider_device import DeviceCiderD
+    from fpnmt.train import capture_sequence
+    refs = _refs(B, V, 3)
+    table = DeviceCiderD.from_corpus(refs, "cuda", max_len=T - 1)
+    g = torch.Generator().manual_seed(5)
+    R, steps = B * n, T - 1
+    hist = torch.randint(4, V // 50, (R, T), generator=g, dtype=torch.int32)
+    hist[:, 0] = 2
+    lens = torch.randint(8, steps + 1, (R,), generator=g, dtype=torch.int32)
+    fin = (lens < steps).int()
+    for r in range(R):
+        if fin[r]:
+            hist[r, 1 + int(lens[r]):] = 3
+    slen = lens + fin
+    hist, slen, fin = hist.cuda(), slen.cuda(), fin.cuda()
+    idx = torch.arange(B, dtype=torch.int32, device="cuda")
+    reward = torch.zeros(R, dtype=torch.float64, device="cuda")
+    score = -torch.rand(R, device="cuda") * 30
+    tok = torch.zeros((R, T), dtype=torch.int64, device="cuda")
+    adv = torch.zeros(R, device="cuda")
+    sc = torch.zeros(3, dtype=torch.float64, device="cuda")
+
+    def f_reward():
+        table.reward(hist, slen, fin, idx, n, reward)
+
+    def f_pack():
+        L.call("fpnmt_scst_pack", B, n, L.SCST_MEAN, reward.data_ptr(), None, hist.data_ptr(), T, slen.data_ptr(),
+               fin.data_ptr(), score.data_ptr(), 2, 3, steps, tok.data_ptr(), T, adv.data_ptr(), sc.data_ptr(),
+               L.stream_ptr())
+
+    fns = {"ciderd_reward": f_reward, "scst_pack": f_pack}
+    for fn in fns.values():
+        fn()
+    torch.cuda.synchronize()
+    assert float(reward.sum()) > 0 and int(tok[:, 0].sum()) == 2 * R
+    graphs = dict(zip(fns, capture_sequence([(lambda fn=fn: [fn() for _ in range(launches)]) for fn in fns.values()])))
+    times = {k: [] for k in graphs}
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for rnd in range(rounds + 1):
+        for name, gr in graphs.items():
+            torch.cuda.synchronize()
+            ev0.record()
+            for _ in range(replays):
+                gr.replay()
+            ev1.record()
+            torch.cuda.synchronize()
+            if rnd:
+                times[name].append(ev0.elapsed_time(ev1) * 1e3 / (replays * launches))
+    out = {"measurement": f"reward kernels alone, {R} rows x {steps} positions, 5 references per image, "
+                          f"{len(table.np['df_keys'])} document n-grams; us per launch ({launches} launches per graph, "
+                          f"{replays} replays per window, {rounds} windows each, alternating)"}
+    out.update({k: _stats(ts, "us", 2) for k, ts in times.items()})
+    print(json.dumps(out), flush=True)
+
+
+def scst_step_bench(B, n, T, V, image, layers, repeats):
+    """(h) the whole self-critical step, end to end (host clock around the
+    call and a device synchronise): the host-reward path (CiderDReward built
+    once over the references, behind a callable) against the device-reward
+    path (DeviceCiderD), two identically built models, alternating calls."""
+    import fpnmt
+    from fpnmt.cider_device import DeviceCiderD
+    from fpnmt.layers import invalidate_weights
+    from fpnmt.scst import SelfCriticalTrainer
+    from fpnmt.train import TrainEngine
+    from utils.cider_reward import CiderDReward
+    fpnmt.set_precision("bf16")
+    refs = _refs(B, V, 3)
+    host = CiderDReward.from_corpus(refs)
+    table = DeviceCiderD.from_corpus(refs, "cuda", max_len=T - 1)
+    img = torch.rand(B, image, image, 3, device="cuda") * 2 - 1
+    trainers = {}
+    for name in ("host_reward", "device_reward"):
+        tr = _model(layers, V, T, image, 2)
+        with torch.no_grad():
+            tr.final_layer.bias[3] += 4.0  # random weights would never end a caption
+        invalidate_weights()
+        trainers[name] = SelfCriticalTrainer(tr, TrainEngine(tr, 1e-6, use_graph=True), 2, 3, T)
+    rewards = {"host_reward": lambda i, c: host(i, c), "device_reward": table}
+    times = {k: [] for k in trainers}
+    for rnd in range(repeats + 2):  # rounds 0 and 1: eager, then the captures
+        for name, tr in trainers.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = tr.step(img, None, n_samples=n, reward=rewards[name], seed=rnd)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            if rnd >= 2:
+                times[name].append((t1 - t0) * 1e3)
+        assert math.isfinite(float(out["loss"]))
+    out = {"measurement": f"self-critical step end to end, {layers}L V {V} {image}^2 T {T} bf16, {B} images, n = {n}, "
+                          f"5 references per image; ms per step (host clock, {repeats} calls each, alternating)"}
+    out.update({k: _stats(ts, "ms") for k, ts in times.items()})
+    print(json.dumps(out), flush=True)
+    fpnmt.set_precision("fp32")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("what", nargs="*", default=["step", "decode", "xent"], choices=["step", "decode", "xent"])
+    ap.add_argument("what", nargs="*", default=["step", "decode", "xent"],
+                    choices=["step", "decode", "xent", "reward", "scst"])
     ap.add_argument("--images", type=int, default=32)
     ap.add_argument("--samples", type=int, default=5)
     ap.add_argument("--vocab", type=int, default=10000)
@@ -206,6 +319,10 @@ def main():
     L.assert_in_tree()
     if "xent" in a.what:
         xent_bench(a.images * a.samples * (a.seq - 1), a.vocab, a.seq - 1, a.launches, a.replays, a.rounds)
+    if "reward" in a.what:
+        reward_bench(a.images, a.samples, a.seq, a.vocab, a.launches, a.replays, a.rounds)
+    if "scst" in a.what:
+        scst_step_bench(a.images, a.samples, a.seq, a.vocab, 224, a.layers, a.repeats)
     if "decode" in a.what:
         decode_bench(a.images, a.samples, a.seq, a.vocab, 224, a.layers, a.repeats)
     if "step" in a.what:
