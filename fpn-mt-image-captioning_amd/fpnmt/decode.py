@@ -34,6 +34,18 @@ rule of the step (fpnmt_beam_step_log) and how the result is chosen
     the final <end>; alpha 0: the raw sum), ties to the lower beam.
 SampleDecoder draws captions instead (fpnmt_sample_step: temperature, top-k,
 nucleus) on the same cache, attention and graphs; its rows never re-rank.
+
+Constrained decoding (mode="beam" and SampleDecoder): no_repeat_ngram,
+repetition_penalty, min_len and banned_tokens. With any of them on, a step
+calls fpnmt_logits_constrain on the fp32 logits before its step kernel, with
+the rows' device-resident history and `fin`, inside the same per-position
+graph: a banned token's logit becomes -inf, which both step kernels already
+define, and a repeated token's logit is penalised once. Scores are then sums
+over the CONSTRAINED logits — beam: score + log_softmax(constrained row);
+sample: l_token - logsumexp(constrained l) — the log-probability under the
+constrained, renormalised distribution, and in sample mode the constraints
+come before temperature, top_k and top_p. With all four at their defaults no
+call is made and the graphs are launch for launch what they were.
 """
 from __future__ import annotations
 
@@ -78,6 +90,48 @@ class _CachedDecoder:
         self.dt = None
         self.graphs = None
         self.qkv_bias = []
+
+    # --------------------------------------------------------- constraints
+    def _set_constraints(self, no_repeat_ngram, repetition_penalty, min_len, banned_tokens, need):
+        """Validates and stores the four constraints (include/fpnmt.h,
+        fpnmt_logits_constrain). need: the finite candidates a row must keep
+        whatever the rules ban (beam_n for a beam search, 1 for a draw)."""
+        if isinstance(no_repeat_ngram, bool) or int(no_repeat_ngram) != no_repeat_ngram or no_repeat_ngram < 0:
+            raise ValueError(f"no_repeat_ngram must be an integer >= 0 (0: off), got {no_repeat_ngram!r}")
+        if not (repetition_penalty > 0.0 and math.isfinite(repetition_penalty)):
+            raise ValueError(f"repetition_penalty must be a finite positive number, got {repetition_penalty!r}")
+        if int(min_len) != min_len or not 0 <= min_len < self.T:
+            raise ValueError(f"min_len must be an integer in [0, max_seq_len = {self.T}), got {min_len!r}")
+        banned = sorted({int(b) for b in banned_tokens})
+        for b in banned:
+            if not 0 <= b < self.V or b == self.end_token:
+                raise ValueError(f"banned token {b}: outside [0, {self.V}) or the end token {self.end_token}")
+        self.no_repeat_ngram, self.repetition_penalty = int(no_repeat_ngram), float(repetition_penalty)
+        self.min_len, self.banned_tokens = int(min_len), tuple(banned)
+        self.constrained = bool(self.no_repeat_ngram or self.repetition_penalty != 1.0 or self.min_len or banned)
+        self.banned_dev = None
+        if not self.constrained:
+            return
+        if self.T > L.CONSTRAIN_MAX_LEN:
+            raise ValueError(f"constrained decoding stages at most {L.CONSTRAIN_MAX_LEN} positions, "
+                             f"max_seq_len is {self.T}")
+        if len(banned) > L.CONSTRAIN_MAX_BANNED:
+            raise ValueError(f"at most {L.CONSTRAIN_MAX_BANNED} banned tokens, got {len(banned)}")
+        # the most the rules can ban in one row: every history token, the list, <end>
+        if self.V - (self.T + 1 + len(banned)) < need:
+            raise ValueError(f"vocabulary {self.V} too small: the constraints can ban {self.T + 1 + len(banned)} "
+                             f"tokens of a row and {need} must stay")
+        if banned:  # built once; the step graphs read it by address
+            self.banned_dev = torch.tensor(banned, dtype=torch.int32,
+                                           device=self.tr.final_layer.kernel.device)
+
+    def _constrain(self, logits, hist, t):
+        """The constraints on the logits of position t, in place, from the
+        rows' history table (fpnmt_logits_constrain); finished rows are left
+        alone."""
+        call("fpnmt_logits_constrain", self.R, self.V, ptr(logits), self.V, ptr(hist), self.T + 1, t, ptr(self.fin),
+             self.no_repeat_ngram, self.repetition_penalty, self.min_len, self.end_token, ptr(self.banned_dev),
+             len(self.banned_tokens), stream_ptr())
 
     def _alloc_cache(self, dev):
         self.kv = torch.empty((max(self.L, 1), self.R, self.T, 2 * self.d), dtype=self.dt, device=dev)
@@ -196,14 +250,25 @@ class _CachedDecoder:
 class BeamDecoder(_CachedDecoder):
     """decode(images) -> list of token-id lists, one per image; in
     mode="beam", decode(images, n_best=k) -> per image the k best
-    (token ids, score) pairs, best first."""
+    (token ids, score) pairs, best first.
+
+    mode="beam" takes the constraints no_repeat_ngram (0: off),
+    repetition_penalty (1: off), min_len (0: off) and banned_tokens: every
+    live beam's logits row is constrained before the step ranks it, so a
+    beam's score is the sum of log_softmax over the constrained rows — its
+    log-probability under the constrained, renormalised distribution.
+    mode="reference" is the reference's own procedure and takes none."""
 
     def __init__(self, transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph=True,
-                 mode="reference", length_alpha=0.0):
+                 mode="reference", length_alpha=0.0, no_repeat_ngram=0, repetition_penalty=1.0, min_len=0,
+                 banned_tokens=()):
         if mode not in ("reference", "beam"):
             raise ValueError(f"mode must be 'reference' or 'beam', got {mode!r}")
         self.mode, self.length_alpha = mode, float(length_alpha)
         super().__init__(transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph)
+        self._set_constraints(no_repeat_ngram, repetition_penalty, min_len, banned_tokens, beam_n)
+        if self.constrained and mode != "beam":
+            raise ValueError("constrained decoding needs mode='beam': mode='reference' is the reference's own procedure")
 
     # ---------------------------------------------------------- buffers
     def _alloc(self, dev):
@@ -247,6 +312,8 @@ class BeamDecoder(_CachedDecoder):
         sin, sout = self.src[t % 2], self.src[(t + 1) % 2]
         logits = self._logits(t, sin)
         if self.mode == "beam":
+            if self.constrained:
+                self._constrain(logits, hin, t)
             call("fpnmt_beam_step_log", self.n_images, self.beam_n, self.V, ptr(logits), self.V, ptr(self.score),
                  ptr(self.blen), ptr(self.fin), ptr(hin), ptr(hout), T + 1, t, ptr(sin), ptr(sout), T,
                  self.end_token, ptr(self.tok), ptr(self.status), s)
@@ -307,10 +374,17 @@ class SampleDecoder(_CachedDecoder):
 
     decode(images, seed=None) -> per image n_samples pairs (token ids without
     <start> and a final <end>, log-probability under the model at temperature
-    1, unfiltered), in sample order."""
+    1, unfiltered), in sample order.
+
+    no_repeat_ngram (0: off), repetition_penalty (1: off), min_len (0: off)
+    and banned_tokens constrain every live row's logits before the draw, and
+    so before temperature, top_k and top_p; the returned log-probability is
+    then the sum of l_token - logsumexp(constrained l): the one under the
+    constrained, renormalised distribution."""
 
     def __init__(self, transformer, n_images, n_samples, max_seq_len, start_token, end_token, use_graph=True,
-                 temperature=1.0, top_k=0, top_p=1.0):
+                 temperature=1.0, top_k=0, top_p=1.0, no_repeat_ngram=0, repetition_penalty=1.0, min_len=0,
+                 banned_tokens=()):
         if n_samples < 1:
             raise ValueError(f"n_samples must be >= 1, got {n_samples}")
         if not (temperature > 0.0 and math.isfinite(temperature)):
@@ -326,6 +400,7 @@ class SampleDecoder(_CachedDecoder):
         filtered = 0 < self.top_k < self.V or self.top_p < 1.0
         if filtered and self.V > L.SAMPLE_FILTER_MAX_VOCAB:
             raise ValueError(f"top_k / top_p need a vocabulary of at most {L.SAMPLE_FILTER_MAX_VOCAB}, got {self.V}")
+        self._set_constraints(no_repeat_ngram, repetition_penalty, min_len, banned_tokens, 1)
         self.n_samples = n_samples
         self._calls = 0
 
@@ -347,6 +422,8 @@ class SampleDecoder(_CachedDecoder):
 
     def _step(self, t):
         logits = self._logits(t, None)
+        if self.constrained:
+            self._constrain(logits, self.hist, t)
         call("fpnmt_sample_step", self.R, self.V, ptr(logits), self.V, self.temperature, self.top_k, self.top_p, 0,
              ptr(self.seed_dev), ptr(self.score), ptr(self.slen), ptr(self.fin), ptr(self.hist), self.T + 1, t,
              self.end_token, ptr(self.tok), None, stream_ptr())

@@ -184,7 +184,8 @@ class Pipeline:
 
     @torch.no_grad()
     def predict_batch(self, images, max_seq_len=None, beam_n=BEAM_SEARCH_N, use_graph=True, mode="reference",
-                      length_alpha=0.0, n_best=1, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None):
+                      length_alpha=0.0, n_best=1, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None,
+                      no_repeat_ngram=0, repetition_penalty=1.0, min_len=0, banned_tokens=()):
         """predict() for a batch of images (n, h, w, 3) at once: the same
         beam procedure per image (pipeline.py:82-154), with a K/V cache and a
         hipGraph per decode step (fpnmt.decode.BeamDecoder). Returns one
@@ -201,22 +202,43 @@ class Pipeline:
         off); seed None: a counter per decoder, a given seed repeats its
         draws) and returns, per image, n_samples (token-id list,
         log-probability) pairs in sample order; beam_n, length_alpha and
-        n_best do not apply."""
+        n_best do not apply.
+
+        Constraints, for mode="beam" and mode="sample" (mode="reference" is
+        the reference's own procedure and raises ValueError with any of them
+        on), applied on the device inside the step (fpnmt_logits_constrain):
+        no_repeat_ngram=g > 0 never lets a g-gram of <start> + caption occur
+        twice; repetition_penalty=p != 1 divides a positive logit of a token
+        already in the caption by p and multiplies a negative one, once per
+        token; min_len keeps <end> out until the caption has min_len tokens;
+        banned_tokens are never emitted. The returned scores are then
+        log-probabilities under the constrained, renormalised distribution,
+        and in sample mode the constraints come before temperature, top_k
+        and top_p."""
         from fpnmt.decode import BeamDecoder, SampleDecoder
         T = max_seq_len or self.max_seq_len
+        try:
+            banned = tuple(sorted({int(b) for b in banned_tokens}))
+        except (TypeError, ValueError):
+            raise ValueError(f"banned_tokens must be a sequence of token ids, got {banned_tokens!r}") from None
+        cons = dict(no_repeat_ngram=no_repeat_ngram, repetition_penalty=repetition_penalty, min_len=min_len,
+                    banned_tokens=banned)
+        ckey = (no_repeat_ngram, repetition_penalty, min_len, banned)
         if mode == "sample":
-            key = (images.shape[0], n_samples, T, use_graph, mode, float(temperature), top_k, float(top_p))
+            key = (images.shape[0], n_samples, T, use_graph, mode, float(temperature), top_k, float(top_p)) + ckey
             dec = getattr(self, "_decoders", {}).get(key)
             if dec is None:
                 dec = SampleDecoder(self.transformer, images.shape[0], n_samples, T, self.start_token, self.end_token,
-                                    use_graph=use_graph, temperature=temperature, top_k=top_k, top_p=top_p)
+                                    use_graph=use_graph, temperature=temperature, top_k=top_k, top_p=top_p, **cons)
                 self.__dict__.setdefault("_decoders", {})[key] = dec
             return dec.decode(images, seed=seed)
         key = (images.shape[0], beam_n, T, use_graph, mode, float(length_alpha))
+        if ckey != (0, 1.0, 0, ()):  # an unconstrained decoder keeps the key it always had
+            key += ckey
         dec = getattr(self, "_decoders", {}).get(key)
         if dec is None:
             dec = BeamDecoder(self.transformer, images.shape[0], beam_n, T, self.start_token, self.end_token,
-                              use_graph=use_graph, mode=mode, length_alpha=length_alpha)
+                              use_graph=use_graph, mode=mode, length_alpha=length_alpha, **cons)
             self.__dict__.setdefault("_decoders", {})[key] = dec
         return dec.decode(images, n_best=n_best)
 

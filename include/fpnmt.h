@@ -22,6 +22,7 @@
  *   fpnmt_beam_step        softmax + top_k + gather + argmax of predict   utils/pipeline.py:115-147
  *   fpnmt_beam_step_log, fpnmt_beam_finalize   beam search proper (log-prob beams, n-best)   not in the reference
  *   fpnmt_sample_step, fpnmt_sample_uniform    sampled decoding (temperature, top-k, top-p)    not in the reference
+ *   fpnmt_logits_constrain                     n-gram blocking, repetition penalty, min length  not in the reference
  *   fpnmt_ciderd_reward, fpnmt_scst_pack       CIDEr-D reward and advantages on the device     not in the reference
  *
  * Conventions (all functions):
@@ -819,6 +820,48 @@ int fpnmt_sample_step(int rows, int vocab, const float* logits, long long ldl, f
                       int32_t* kept_out /* may be NULL */, fpnmt_stream_t stream);
 int fpnmt_sample_uniform(int rows, int t, unsigned long long seed, const long long* seed_dev, float* u_out,
                          fpnmt_stream_t stream);
+
+/* Constrained decoding (not in the reference; csrc/constrain.hip): rewrites
+ * the fp32 logits (rows, vocab) of a decode position in place, before
+ * fpnmt_beam_step_log or fpnmt_sample_step, from the rows' token history on
+ * the device. A ban is a -inf logit, which both step kernels define: weight 0
+ * in the draw, exp(-inf - max) = 0 in the logsumexp and a -inf candidate. The
+ * step's scores are therefore sums over the CONSTRAINED logits (beam: score +
+ * log_softmax(constrained row); sample: l_token - logsumexp(constrained l)),
+ * the log-probability under the constrained, renormalised distribution; in
+ * sampled decoding the constraints come before temperature, top_k and top_p.
+ * A row r with fin != NULL and fin[r] != 0 is neither read nor written. For
+ * every other row, with h[0..t] = hist[r*hist_ld + 0..t] (h[0] is <start>;
+ * the token being chosen is number t + 1) and l = logits + r*ldl, the final
+ * value of l[j], 0 <= j < vocab, is
+ *   -inf, if one of
+ *     n-gram   g = no_repeat_ngram > 0 and an i in [0, t - g + 1] exists with
+ *              h[i .. i+g-2] == h[t-g+2 .. t] and h[i+g-1] == j: the g - 1
+ *              tokens before the one being chosen open an earlier complete
+ *              g-gram that j would complete again (g == 1: every token of
+ *              h[0..t]; g > t + 1: none);
+ *     list     j is one of banned[0 .. n_banned);
+ *     length   j == end_token and t < min_len (<end> now would give a caption
+ *              of t tokens);
+ *   else l[j] > 0 ? l[j] / p : l[j] * p (p = repetition_penalty, one IEEE fp32
+ *     divide or multiply), if p != 1 and j occurs in h[0..t]: applied exactly
+ *     once however often j occurs; a NaN keeps its bits, -inf stays -inf;
+ *   else unchanged, bit for bit. Columns vocab .. ldl-1 are never written.
+ * History or banned ids outside [0, vocab) are ignored: they match nothing
+ * (not even each other) and no address is formed from them.
+ * FPNMT_E_ARG: null logits / hist, rows <= 0, vocab <= 0, ldl < vocab, t < 0,
+ * hist_ld < t + 1, no_repeat_ngram < 0, min_len < 0, repetition_penalty not
+ * finite or <= 0, end_token outside [0, vocab), n_banned < 0, or n_banned > 0
+ * with banned NULL. FPNMT_E_UNSUPPORTED: t + 1 > FPNMT_CONSTRAIN_MAX_LEN (the
+ * history row is staged in LDS), n_banned > FPNMT_CONSTRAIN_MAX_BANNED. With
+ * every rule off (no_repeat_ngram 0, repetition_penalty 1, min_len <= t,
+ * n_banned 0) nothing is launched.                                          */
+#define FPNMT_CONSTRAIN_MAX_LEN    1024   /* t + 1 positions staged per row */
+#define FPNMT_CONSTRAIN_MAX_BANNED 4096
+int fpnmt_logits_constrain(int rows, int vocab, float* logits, long long ldl, const int32_t* hist, int hist_ld, int t,
+                           const int32_t* fin /* may be NULL */, int no_repeat_ngram, float repetition_penalty,
+                           int min_len, int end_token, const int32_t* banned /* may be NULL */, int n_banned,
+                           fpnmt_stream_t stream);
 
 /* Device-side CIDEr-D reward (not in the reference; csrc/cider.hip): the
  * arithmetic of utils/cider_reward.py CiderDReward (n = 4, clipped counts,
