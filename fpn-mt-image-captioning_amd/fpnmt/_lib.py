@@ -209,6 +209,8 @@ SIGNATURES = {
     "fpnmt_xent_fwd_bwd": [I, LL, I, P, LL, P, P, P, LL, F, P],
     "fpnmt_xent_weighted_fwd_bwd": [I, LL, I, P, LL, P, P, I, P, P, P, LL, F, P],
     "fpnmt_repeat_rows": [I, I, I, LL, P, P, P],
+    "fpnmt_xent_smooth_fwd_bwd": [I, LL, I, P, LL, P, F, P, P, P, P, LL, F, P],
+    "fpnmt_caption_stats": [LL, I, P, P, P, P, P, P, P, I, P],
     "fpnmt_grad_sumsq": [I, P, P, I, P, P, P, F, P, P],
     "fpnmt_amsgrad_step": [C.POINTER(AdamDesc), I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P],
     "fpnmt_amsgrad_step_prep": [C.POINTER(AdamDesc), I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P],

@@ -2185,6 +2185,67 @@ class WeightedXentFn(torch.autograd.Function):
         return dlog.reshape(ctx.shape), None, None, None, None
 
 
+class SmoothedXentFn(torch.autograd.Function):
+    """MaskedXentFn against the label-smoothed target (1 - eps) * onehot +
+    eps / V (Keras CategoricalCrossentropy(label_smoothing=eps)), still a
+    mean over ALL rows (fpnmt_xent_smooth_fwd_bwd: the row is read once). The
+    gradient is computed in the same launch (saved) — the loss must be the
+    root of backward."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, eps):
+        v = logits.shape[-1]
+        lg = logits.reshape(-1, v)
+        if lg.dtype != torch.float32:
+            raise TypeError("SmoothedXentFn expects fp32 logits")
+        lg = lg.contiguous()
+        lab = labels.reshape(-1).to(torch.int32).contiguous()
+        rows = lg.shape[0]
+        loss = torch.empty((1,), dtype=torch.float32, device=lg.device)
+        need = ctx.needs_input_grad[0]
+        dlog = torch.empty_like(lg) if need else None
+        call("fpnmt_xent_smooth_fwd_bwd", L.F32, rows, v, ptr(lg), v, ptr(lab), float(eps), ptr(loss), None, None,
+             ptr(dlog), v, 1.0, stream_ptr())
+        if need:
+            ctx.save_for_backward(dlog)
+        ctx.shape = logits.shape
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dlog,) = ctx.saved_tensors
+        return dlog.reshape(ctx.shape), None, None
+
+
+def caption_eval(logits, labels, eps, totals, accumulate):
+    """The held-out statistics of teacher-forced logits (captions, t, V) fp32
+    against labels (captions, t): the smoothed loss in the step's convention
+    and, per caption, the unsmoothed log-probability, the length and the
+    number of arg-max hits (fpnmt_xent_smooth_fwd_bwd without a gradient, then
+    fpnmt_caption_stats). totals (3,) f64 on the device receives the sums of
+    log-probability, tokens and hits: overwritten, or added to with
+    accumulate. Returns (loss, caption_logp, caption_len, caption_hit)."""
+    if logits.dtype != torch.float32 or logits.dim() != 3:
+        raise TypeError("caption_eval expects (captions, t, V) fp32 logits")
+    if totals.dtype != torch.float64 or totals.numel() != 3 or not totals.is_contiguous():
+        raise TypeError("caption_eval: totals must be a contiguous (3,) float64 tensor")
+    n, t, v = logits.shape
+    lg = logits.contiguous()
+    lab = labels.reshape(-1).to(torch.int32).contiguous()
+    dev = lg.device
+    loss = _empty((1,), torch.float32, dev)
+    logp = _empty((n * t,), torch.float32, dev)
+    hit = _empty((n * t,), torch.int32, dev)
+    cap_logp = _empty((n,), torch.float32, dev)
+    cap_len = _empty((n,), torch.int32, dev)
+    cap_hit = _empty((n,), torch.int32, dev)
+    call("fpnmt_xent_smooth_fwd_bwd", L.F32, n * t, v, ptr(lg), v, ptr(lab), float(eps), ptr(loss), ptr(logp),
+         ptr(hit), None, 0, 1.0, stream_ptr())
+    call("fpnmt_caption_stats", n, t, ptr(lab), ptr(logp), ptr(hit), ptr(cap_logp), ptr(cap_len), ptr(cap_hit),
+         ptr(totals), 1 if accumulate else 0, stream_ptr())
+    return loss.reshape(()), cap_logp, cap_len, cap_hit
+
+
 class RepeatRowsFn(torch.autograd.Function):
     """y[i * n + s] = x[i] for s < n (torch.repeat_interleave(x, n, 0)): the
     encoder output of B images as the B * n rows the decoder trains n

@@ -58,8 +58,11 @@ from .layers import group_param_order
 class TrainEngine:
     def __init__(self, transformer, schedule, beta1=0.9, beta2=0.98, eps=1e-9, clipnorm=1.0, use_graph=True,
                  group=None, bucket_bytes=fdist.DEFAULT_BUCKET_BYTES, split_backward=None, bucket_dtype=None,
-                 sync_bn=True):
+                 sync_bn=True, label_smoothing=0.0):
         from models.transformer import create_masks  # noqa: F401 (ensures import path)
+        if not 0.0 <= float(label_smoothing) < 1.0:  # NaN fails both comparisons
+            raise ValueError(f"TrainEngine: label_smoothing must lie in [0, 1), got {label_smoothing!r}")
+        self.label_smoothing = float(label_smoothing)
         self.model = transformer
         self.schedule = schedule
         self.adam = dict(beta1=beta1, beta2=beta2, eps=eps, clipnorm=clipnorm)
@@ -143,6 +146,9 @@ class TrainEngine:
         self.graphs = None
         self.static = None
         self._wsteps = {}  # step_weighted: shapes -> [calls, graphs, static]
+        self._esteps = {}  # eval_step: shapes -> [calls, graph, static inputs, outputs]
+        self._eval_gen = -1  # the compute copies' generation the eval graphs last saw
+        self.eval_totals = torch.zeros(3, dtype=torch.float64, device=dev)  # eval_step(accumulate=True)
 
     # ------------------------------------------------------------ pieces
     def _one(self, loss):
@@ -186,6 +192,8 @@ class TrainEngine:
         enc = enc_fn()
         if weights is None:
             dec, _ = m.decoder(tar_inp, enc, True, mask, None)
+            if self.label_smoothing > 0.0:
+                return ops.SmoothedXentFn.apply(m.final_layer(dec), tar_real, self.label_smoothing)
             return ops.MaskedXentFn.apply(m.final_layer(dec), tar_real)
         dec, _ = m.decoder(tar_inp, ops.RepeatRowsFn.apply(enc, tok.shape[0] // enc.shape[0]), True, mask, None)
         return ops.WeightedXentFn.apply(m.final_layer(dec), tar_real, weights, tok.shape[1] - 1)
@@ -387,7 +395,9 @@ class TrainEngine:
         (1 / rows) * sum_r weights[r // (T_full - 1)] * mask_r * ce_r. Returns
         the (device) loss. The first call at a shape runs eagerly, the second
         captures, later ones copy image, tokens and weights into the static
-        buffers and replay."""
+        buffers and replay. The engine's label_smoothing does not apply here:
+        a self-critical step has no one-hot target to soften, and its results
+        are the same bits whatever label_smoothing is."""
         B = img.shape[0]
         if tok.dim() != 2 or B < 1 or tok.shape[0] % B or tok.shape[0] == 0:
             raise ValueError(f"step_weighted: {tuple(tok.shape)} captions for {B} images")
@@ -407,6 +417,72 @@ class TrainEngine:
         static[1].copy_(tok)
         static[3].copy_(weights)
         return self._replay(graphs, static[2])
+
+    # ---------------------------------------------------------- held out
+    def reset_eval_totals(self):
+        """Zero the running sums eval_step(accumulate=True) adds to."""
+        self.eval_totals.zero_()
+
+    def _eval_forward(self, img, tok, n, accumulate):
+        m = self.model
+        totals = self.eval_totals if accumulate else torch.empty(3, dtype=torch.float64, device=img.device)
+        tar_inp, tar_real, mask = ops.decoder_targets(tok)
+        enc = m.encoder(img, False, None)
+        if n > 1:
+            enc = ops.RepeatRowsFn.apply(enc, n)
+        dec, _ = m.decoder(tar_inp, enc, False, mask, None)
+        loss, logp, ln, hit = ops.caption_eval(m.final_layer(dec), tar_real, self.label_smoothing, totals,
+                                               accumulate)
+        return {"loss": loss, "caption_logp": logp, "caption_len": ln, "caption_hit": hit, "totals": totals}
+
+    @torch.no_grad()
+    def eval_step(self, img, tok, n_per_image=1, accumulate=False):
+        """The held-out form of step(): the loss of (img, tok) without an
+        update. The model runs in inference mode (no dropout, BatchNorm on its
+        moving statistics), the encoder once per image with n_per_image
+        captions each (tok (B * n_per_image, T_full), image-major), and the
+        loss launch (fpnmt_xent_smooth_fwd_bwd without a gradient, at the
+        engine's label_smoothing) also gives each position's log-probability
+        and arg-max hit, which fpnmt_caption_stats sums per caption.
+
+        Returns device tensors only: "loss" (the step's convention: the
+        smoothed CE, a mean over all rows), "caption_logp" (rows,) fp32 (the
+        unsmoothed teacher-forced log-probability, <end> included),
+        "caption_len" / "caption_hit" (rows,) int32, "totals" (3,) f64 = the
+        sums of log-probability, tokens and hits. accumulate=True adds the
+        sums to the engine's eval_totals (reset_eval_totals() zeroes them) and
+        returns that tensor as "totals".
+
+        Nothing is written: no parameter, gradient, optimizer state, moving
+        statistic or dropout counter. Per shape the first call runs eagerly,
+        the second captures, later ones copy image and tokens into static
+        buffers and replay (their outputs are then the graph's static tensors,
+        overwritten by the next replay); there is no host synchronisation."""
+        B, n = img.shape[0], int(n_per_image)
+        if tok.dim() != 2 or B < 1 or n < 1 or tok.shape[0] != B * n or tok.shape[1] < 2:
+            raise ValueError(f"eval_step: {tuple(tok.shape)} captions for {B} images x {n}")
+        dt = fpnmt.compute_dtype()
+        key = (tuple(img.shape), tuple(tok.shape), tok.dtype, img.dtype, n, bool(accumulate), dt)
+        ent = self._esteps.setdefault(key, [0, None, None, None])
+        ent[0] += 1
+        if not self.use_graph or ent[0] == 1:
+            flayers.prepare_all(self.model, dt)
+            self._eval_gen = flayers._GEN[0]
+            return self._eval_forward(img, tok, n, accumulate)
+        if self._eval_gen != flayers._GEN[0]:
+            # parameters edited by hand / loaded since (a step or a checkpoint
+            # restore refreshes the copies itself, in the buffers the graph reads)
+            flayers.prepare_all(self.model, dt)
+            self._eval_gen = flayers._GEN[0]
+        if ent[1] is None:
+            s_img, s_tok = img.detach().clone(), tok.detach().clone()
+            out = {}
+            ent[1] = capture_sequence([lambda: out.update(self._eval_forward(s_img, s_tok, n, accumulate))])[0]
+            ent[2], ent[3] = (s_img, s_tok), out
+        ent[2][0].copy_(img)
+        ent[2][1].copy_(tok)
+        ent[1].replay()
+        return dict(ent[3])
 
     def _replay(self, graphs, loss):
         """Replay one captured step (the exchanges between its graphs)."""

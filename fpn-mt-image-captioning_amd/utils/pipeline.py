@@ -55,7 +55,7 @@ class Pipeline:
     def __init__(self, tokenizer_filename=None, checkpoint_path=None, max_seq_len=32, target_vocab_size=None,
                  image_size=IMAGE_INPUT_SIZE, n_layers=num_layers, backbone=None, rate=DROPOUT_RATE,
                  device="cuda", init=None, use_graph=True, clipnorm_mode=CLIPNORM_MODE, max_to_keep=100,
-                 data_dir=DATADIR, data_type_val=DATATYPE_VAL):
+                 data_dir=DATADIR, data_type_val=DATATYPE_VAL, label_smoothing=0.0):
         self.max_seq_len = max_seq_len
         self._metric_eval_src = (data_dir, data_type_val)
         self._metric_eval = None
@@ -74,7 +74,8 @@ class Pipeline:
                                        rate, max_seq_len=self.max_seq_len, backbone=backbone, init=init).to(device)
         self.learning_rate = CustomSchedule(dff, WARM_UP_STEPS)  # pipeline.py:29 (d_model arg = dff)
         self.engine = TrainEngine(self.transformer, self.learning_rate, beta1=0.9, beta2=0.98, eps=1e-9,
-                                  clipnorm=clipnorm_for(clipnorm_mode), use_graph=use_graph)
+                                  clipnorm=clipnorm_for(clipnorm_mode), use_graph=use_graph,
+                                  label_smoothing=label_smoothing)  # not in the reference; 0: its one-hot loss
         self.optimizer = self.engine
         self.train_loss = Mean(name="train_loss")  # pipeline.py:35
         self.checkpoint_path = checkpoint_path
@@ -156,6 +157,60 @@ class Pipeline:
                                                   self.max_seq_len)
         return tr.step(img, refs, n_samples=n_samples, baseline=baseline, reward=reward, temperature=temperature,
                        top_k=top_k, top_p=top_p, seed=seed, image_keys=image_keys)
+
+    # ----------------------------------------------------------- held out
+    def eval_step(self, img, caption_token):
+        """The loss of one held-out batch without an optimizer step (not in the
+        reference): the model in inference mode, nothing written. Returns the
+        device tensors of TrainEngine.eval_step: "loss" (comparable with
+        train_loss at the same label_smoothing), per caption "caption_logp",
+        "caption_len", "caption_hit", and "totals" (3,) f64."""
+        return self.engine.eval_step(img, caption_token)
+
+    def validate(self, batches):
+        """Held-out loss over an iterable of (img, caption_token) batches, of
+        any shapes (a short last batch runs eagerly, as in train_step). The
+        sums of log-probability, tokens and arg-max hits accumulate on the
+        device; one read-back at the end. Returns fpnmt.evalstats.summarize's
+        dict: "token_nll", "perplexity" = exp(token_nll), "token_accuracy",
+        "tokens", "captions", "totals". Under data parallelism every rank
+        validates its shard; the totals are plain sums and add. An empty
+        iterable raises ValueError."""
+        from fpnmt.evalstats import summarize
+        eng = self.engine
+        eng.reset_eval_totals()
+        captions = 0
+        for img, tok in batches:
+            eng.eval_step(img, tok, accumulate=True)
+            captions += int(tok.shape[0])
+        if captions == 0:
+            raise ValueError("validate: no batches")
+        return summarize(eng.eval_totals.cpu().tolist(), captions)
+
+    def score_captions(self, images, captions, n_per_image=1):
+        """Teacher-forced log-probabilities of given captions: images
+        (B, H, W, 3) on the GPU, captions B * n_per_image token-id lists
+        without <start> / <end>, image-major. Returns per caption
+        (log_probability, length), the final <end> counted: the score
+        convention of predict_batch's mode="beam" (length_alpha 0) and
+        mode="sample", so n-best lists and external captions can be reranked
+        with it. A caption of more than max_seq_len - 1 tokens raises
+        ValueError."""
+        from fpnmt.scst import pack_tokens
+        caps = [[int(t) for t in c] for c in captions]
+        n = int(n_per_image)
+        if n < 1 or len(caps) != images.shape[0] * n:
+            raise ValueError(f"score_captions: {len(caps)} captions for {images.shape[0]} images x {n_per_image}")
+        T = self.max_seq_len
+        long = [i for i, c in enumerate(caps) if len(c) > T - 1]
+        if long:
+            raise ValueError(f"score_captions: caption {long[0]} has {len(caps[long[0]])} tokens, "
+                             f"more than max_seq_len - 1 = {T - 1}")
+        # <start> ids <end> 0...: T + 1 columns, so that a caption of T - 1 tokens keeps its <end>
+        tok = torch.from_numpy(pack_tokens(caps, T + 1, self.start_token, self.end_token, T)).to(images.device)
+        out = self.engine.eval_step(images, tok, n_per_image=n)
+        logp, ln = out["caption_logp"].cpu().tolist(), out["caption_len"].cpu().tolist()
+        return list(zip(logp, ln))
 
     # ------------------------------------------------------------ predict
     @torch.no_grad()

@@ -644,6 +644,45 @@ int fpnmt_xent_weighted_fwd_bwd(int dtype, long long rows, int v, const float* l
  * is fpnmt_rowsum_groups(dtype, 1, b, n, len, {dy}, dx_f32, dx, ...).        */
 int fpnmt_repeat_rows(int dtype, int b, int n, long long len, const void* x, void* y, fpnmt_stream_t stream);
 
+/* ---- label-smoothed masked cross-entropy, gradient optional ---------------
+ * The masked CE against the target (1 - eps) * onehot + eps / v (Keras
+ * CategoricalCrossentropy(label_smoothing=eps)), mask_r = label_r in (0, v),
+ * lse_r = logsumexp(logits[r, :]):
+ *   ce_r         = lse_r - (1 - eps) * logits[r, label_r] - (eps / v) * sum_j logits[r, j]
+ *   loss         = (1 / rows) * sum_r mask_r * ce_r   (a mean over ALL rows;
+ *                  scalar, overwritten; summed in row order through the
+ *                  workspace: bitwise repeatable),
+ *   dlogits[r,j] = dloss_scale * mask_r / rows * (softmax_j - (1 - eps) [j == label_r] - eps / v)
+ *                  (dtype bf16 or fp32; may be NULL: the evaluation form, the
+ *                  row is then read once at every width; exact zeros on a pad),
+ *   row_logp[r]  = logits[r, label_r] - lse_r, the UNSMOOTHED log-probability,
+ *                  0 on a pad (may be NULL),
+ *   row_hit[r]   = 1 when the lowest-index arg-max of the row is label_r, else
+ *                  0; 0 on a pad (may be NULL). Float comparisons only: exact.
+ * fp32 logits; a pad label is never dereferenced. Each row is read once and
+ * held in registers up to v = 10 240 (wider rows with a gradient: twice).
+ * No allocation, no synchronisation, capturable.
+ * FPNMT_E_ARG: eps outside [0, 1) or NaN, null loss / logits / labels, a bad
+ * dtype, v < 1, ld < v, ldd < v with a gradient, rows outside [0, 2^31), no
+ * workspace attached.                                                        */
+int fpnmt_xent_smooth_fwd_bwd(int dtype, long long rows, int v, const float* logits, long long ld,
+                              const int32_t* labels, float eps, float* loss, float* row_logp, int32_t* row_hit,
+                              void* dlogits, long long ldd, float dloss_scale, fpnmt_stream_t stream);
+
+/* ---- per-caption and total statistics of a teacher-forced batch -----------
+ * Rows are captions * t, caption-major; a position is live when its label is
+ * > 0. Per caption: cap_logp = the sum of row_logp over its live positions
+ * (ascending, fp64, rounded once to fp32), cap_len = their number, cap_hit =
+ * the sum of row_hit over them (each may be NULL). totals[0..2] = the sums of
+ * log-probability, tokens and hits over all captions as fp64, added in caption
+ * order by one block; accumulate == 0 overwrites them, non-zero adds to what
+ * they hold (a validation loop's running sums, no framework add).
+ * FPNMT_E_ARG: null labels / row_logp / row_hit / totals, t < 1, captions < 0,
+ * captions * t >= 2^31.                                                      */
+int fpnmt_caption_stats(long long captions, int t, const int32_t* labels, const float* row_logp,
+                        const int32_t* row_hit, float* cap_logp, int32_t* cap_len, int32_t* cap_hit, double* totals,
+                        int accumulate, fpnmt_stream_t stream);
+
 /* ---- optimizer: Keras Adam(amsgrad) + per-tensor clip_by_norm ----------
  * Tensors are segments [off[i], off[i+1]) of flat fp32 arrays, processed in
  * blocks of block_elems that never cross a segment: block b covers
