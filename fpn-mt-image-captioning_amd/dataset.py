@@ -88,8 +88,11 @@ def build_caption_tokens(captions, tokenizer_file=TOKENIZER_FILENAME, num_words=
 
 def get_coco_images_dataset(dataDir, dataType, n_test=None, tokenizer_file=TOKENIZER_FILENAME,
                             batch_size=BATCH_SIZE, image_size=IMAGE_INPUT_SIZE, dtype=torch.float32, seed=0,
-                            threads=8, device="cuda"):
-    """dataset.py:29-94 -> (loader, max_seq_len, set_len)."""
+                            threads=8, device="cuda", augment=None, cache_bytes=0):
+    """dataset.py:29-94 -> (loader, max_seq_len, set_len). augment (an
+    fpnmt.input_pipeline.Augment) and cache_bytes go to the loader: train-time
+    augmentation on the device and a cache of decoded images by path (one
+    entry for an image's several captions); off by default."""
     from fpnmt.input_pipeline import ImageBatchLoader
 
     coco = COCO("{}/annotations/captions_{}.json".format(dataDir, dataType))
@@ -101,7 +104,7 @@ def get_coco_images_dataset(dataDir, dataType, n_test=None, tokenizer_file=TOKEN
     imgs = coco.loadImgs(img_ids)
     img_paths = [os.path.join(dataDir, "images", dataType, img["file_name"]) for img in imgs]
     loader = ImageBatchLoader(img_paths, captions_token, batch_size, image_size, dtype=dtype, shuffle=True,
-                              seed=seed, threads=threads, device=device)
+                              seed=seed, threads=threads, device=device, augment=augment, cache_bytes=cache_bytes)
     return loader, max_seq_len, set_len
 
 

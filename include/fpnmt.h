@@ -1050,6 +1050,45 @@ int fpnmt_image_resize_normalize(const fpnmt_image_item* items_dev, int n, const
                                  long long pixel_bytes, int max_w, int out_h, int out_w, float div, float sub,
                                  int dtype, void* out, fpnmt_stream_t stream);
 
+/* ---- train-time augmentation of the same packed batch ------------------
+ * One fpnmt_image_aug per image, in device memory: a crop box in source
+ * pixels, a left-right mirror and three colour factors.
+ *   out[i] = normalise(colour(resize(box of image i, mirrored if flip)))
+ * resize: the bilinear formula above with in_size = ch / cw and the source
+ * indices offset by y0 / x0; with flip, box column k is read at source
+ * column x0 + cw - 1 - k. The colour steps run on the resized fp32 value
+ * v in [0, 255] in this order, every multiply and add rounded separately,
+ * with a clamp to [0, 255] after each executed step:
+ *   contrast   (c != 1 and sums != NULL): v = m + (v - m) * c, where
+ *              m = (float)((double)(299 S_R + 587 S_G + 114 S_B) /
+ *              (double)(1000 ch cw)) is the mean luma of the SOURCE box from
+ *              its integer byte sums (fpnmt_image_crop_stats);
+ *   brightness (b != 1): v = v * b;
+ *   saturation (s != 1): g = 0.299f r + 0.587f g + 0.114f b (left to right),
+ *              v = g + (v - g) * s.
+ * Then v / div - sub. A factor of exactly 1.0f SKIPS its step, so the
+ * identity record (full box, no flip, factors 1) reproduces
+ * fpnmt_image_resize_normalize bit for bit. The records are device data the
+ * entry cannot check: the kernels clamp a box to its image, and a box or an
+ * image with no pixels writes zeros. max_cw >= every box's cw sizes the LDS
+ * window (a wider box is read from global memory instead).
+ *
+ * fpnmt_image_crop_stats writes sums[4 i + 0..2] = the R, G, B byte sums of
+ * image i's (clamped) box and sums[4 i + 3] = 0. It zeroes `sums` itself on
+ * the stream; integer sums do not depend on the order the blocks finish in. */
+typedef struct fpnmt_image_aug {
+  int y0, x0, ch, cw; /* crop box in source pixels, inside the image, ch, cw >= 1 */
+  int flip;           /* 1: mirror the box left-right */
+  float brightness, contrast, saturation; /* factors; exactly 1.0f = step skipped */
+} fpnmt_image_aug;
+int fpnmt_image_crop_stats(const fpnmt_image_item* items_dev, const fpnmt_image_aug* aug_dev, int n,
+                           const uint8_t* pixels, long long pixel_bytes, unsigned long long* sums,
+                           fpnmt_stream_t stream);
+int fpnmt_image_augment_resize_normalize(const fpnmt_image_item* items_dev, const fpnmt_image_aug* aug_dev,
+                                         const unsigned long long* sums, int n, const uint8_t* pixels,
+                                         long long pixel_bytes, int max_cw, int out_h, int out_w, float div,
+                                         float sub, int dtype, void* out, fpnmt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
