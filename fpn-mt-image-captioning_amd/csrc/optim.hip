@@ -123,12 +123,17 @@ __global__ __launch_bounds__(256) void wprep_batched_kernel(const fpnmt_wprep_it
 // Per-block partial ||g||^2 (block = a <= block_elems run of one segment);
 // amsgrad_kernel sums a segment's partials in block order (no atomics: the
 // clip factor, and so every update, is the same on every run).
+template <bool GROUPS>
 __device__ __forceinline__ void sumsq_block(int blk, const int32_t* __restrict__ blk_seg,
                                             const long long* __restrict__ blk_start, int block_elems,
                                             const long long* __restrict__ off, const int32_t* __restrict__ seg_flags,
+                                            const fpnmt_seg_group* __restrict__ groups,
                                             const float* __restrict__ g, float gs, float* __restrict__ blk_part,
                                             float* red) {
   const int seg = blk_seg[blk];
+  if constexpr (GROUPS) {
+    if (groups[seg].frozen) return;  // uniform per block: no gradient is read, no partial written
+  }
   if (seg_flags && (seg_flags[seg] & 1)) return;
   const long long b0 = blk_start[blk];
   const long long b1 = min(b0 + block_elems, off[seg + 1]);
@@ -154,15 +159,17 @@ __device__ __forceinline__ void sumsq_block(int blk, const int32_t* __restrict__
 
 // one workgroup per arena block, or a persistent grid striding over them
 // (gridDim.x < nblocks: the early optimizer part beside a running backward)
+template <bool GROUPS>
 __global__ __launch_bounds__(256) void sumsq_kernel(int blk_first, int nblocks, const int32_t* __restrict__ blk_seg,
                                                     const long long* __restrict__ blk_start, int block_elems,
                                                     const long long* __restrict__ off,
                                                     const int32_t* __restrict__ seg_flags,
+                                                    const fpnmt_seg_group* __restrict__ groups,
                                                     const float* __restrict__ g, float gs,
                                                     float* __restrict__ blk_part) {
   __shared__ float red[4];
   for (int b = (int)blockIdx.x; b < nblocks; b += (int)gridDim.x)
-    sumsq_block(blk_first + b, blk_seg, blk_start, block_elems, off, seg_flags, g, gs, blk_part, red);
+    sumsq_block<GROUPS>(blk_first + b, blk_seg, blk_start, block_elems, off, seg_flags, groups, g, gs, blk_part, red);
 }
 
 __device__ __forceinline__ float sched_lr(const fpnmt_adam_desc& d, float step) {
@@ -185,7 +192,10 @@ __device__ __forceinline__ uint32_t prep_div_c(uint32_t q, const fpnmt_seg_prep&
   return (uint32_t)(((((uint64_t)q * pp.c_magic) >> 32) + q) >> pp.c_shift);
 }
 
-template <bool PREP>
+// GROUPS: groups[seg] (uniform per block, one 16-B load like preps[seg]) scales
+// the rate, adds decoupled weight decay and marks frozen segments, whose
+// blocks return before any load of the arena, the norms or the prep table.
+template <bool PREP, bool GROUPS>
 __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk, const int32_t* __restrict__ blk_seg,
                                               const long long* __restrict__ blk_start, int block_elems,
                                               const long long* __restrict__ off,
@@ -195,9 +205,17 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
                                               const float* __restrict__ sumsq, const float* __restrict__ blk_part,
                                               const int32_t* __restrict__ seg_blk0,
                                               const long long* __restrict__ step,
-                                              const fpnmt_seg_prep* __restrict__ preps, float& s_ss,
+                                              const fpnmt_seg_prep* __restrict__ preps,
+                                              const fpnmt_seg_group* __restrict__ groups, float& s_ss,
                                               unsigned short* s_prep) {
   const int seg = blk_seg[blk];
+  float g_scale = 1.f, g_decay = 0.f;
+  if constexpr (GROUPS) {
+    const fpnmt_seg_group gp = groups[seg];
+    if (gp.frozen) return;
+    g_scale = gp.lr_scale;
+    g_decay = gp.weight_decay;
+  }
   const bool sparse_norm = seg_flags && (seg_flags[seg] & 1);
   if (d.clipnorm > 0.f && !sparse_norm && threadIdx.x < 64) {
     // the segment's ||g||^2: its blocks' partials in block order (wave 0)
@@ -213,7 +231,12 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
   const float lr = sched_lr(d, it);
   const float t = it + 1.f;
   const float b1p = powf(d.beta1, t), b2p = powf(d.beta2, t);
-  const float alpha = lr * sqrtf(1.f - b2p) / (1.f - b1p);
+  const float alpha_1 = lr * sqrtf(1.f - b2p) / (1.f - b1p);
+  // alpha * 1 is alpha: the all-default table gives the plain step's bits
+  const float alpha = GROUPS ? alpha_1 * g_scale : alpha_1;
+  // decoupled (AdamW-style) decay on the old parameter; not evaluated at 0
+  const bool decay = GROUPS && g_decay != 0.f;
+  const float lsw = lr * g_scale * g_decay;
   // tf.clip_by_norm: g * clip / max(||g||, clip)  (||g|| = 0 -> factor 1)
   const float ss = d.clipnorm > 0.f ? (sparse_norm ? sumsq[seg] * d.grad_scale * d.grad_scale : s_ss) : 0.f;
   const float nrm = ss > 0.f ? sqrtf(ss) : 0.f;
@@ -230,7 +253,11 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
       vi = vi + (g * g - vi) * (1.f - d.beta2);
     }
     hi = fmaxf(hi, vi);
+    const float pold = pi;
     pi = pi - (mi * alpha) / (sqrtf(hi) + d.eps);
+    if constexpr (GROUPS) {
+      if (decay) pi = pi - lsw * pold;
+    }
   };
   // float4 body (block starts are 4-element aligned), U vectors per thread in
   // flight per array (all 5U loads issued before the first use); streaming
@@ -356,7 +383,7 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
 // one workgroup per arena block, or a persistent grid striding over them
 // (gridDim.x < nblocks: the early optimizer part, no compute-copy refresh,
 // sharing the CUs with a running backward)
-template <bool PREP>
+template <bool PREP, bool GROUPS>
 __global__ __launch_bounds__(256) void amsgrad_kernel(fpnmt_adam_desc d, int blk_first, int nblocks,
                                                       const int32_t* __restrict__ blk_seg,
                                                       const long long* __restrict__ blk_start, int block_elems,
@@ -368,13 +395,14 @@ __global__ __launch_bounds__(256) void amsgrad_kernel(fpnmt_adam_desc d, int blk
                                                       const float* __restrict__ blk_part,
                                                       const int32_t* __restrict__ seg_blk0,
                                                       const long long* __restrict__ step,
-                                                      const fpnmt_seg_prep* __restrict__ preps) {
+                                                      const fpnmt_seg_prep* __restrict__ preps,
+                                                      const fpnmt_seg_group* __restrict__ groups) {
   __shared__ float s_ss;
   __shared__ unsigned short s_prep[PREP ? PREP_LDS : 1];
   for (int b = (int)blockIdx.x; b < nblocks; b += (int)gridDim.x) {
     if (b != (int)blockIdx.x) __syncthreads();  // the previous block's LDS reads are done
-    amsgrad_block<PREP>(d, blk_first + b, blk_seg, blk_start, block_elems, off, seg_flags, param, grad, m, v, vhat,
-                        sumsq, blk_part, seg_blk0, step, preps, s_ss, s_prep);
+    amsgrad_block<PREP, GROUPS>(d, blk_first + b, blk_seg, blk_start, block_elems, off, seg_flags, param, grad, m, v,
+                                vhat, sumsq, blk_part, seg_blk0, step, preps, groups, s_ss, s_prep);
   }
 }
 
@@ -427,17 +455,39 @@ int fpnmt_weight_prep_batched(const fpnmt_wprep_item* items_dev, int n_items, lo
   return check_launch("weight_prep_batched");
 }
 
-int fpnmt_grad_sumsq_part(int blk_first, int nblocks, int max_grid, const int32_t* blk_seg,
-                          const long long* blk_start, int block_elems, const long long* off,
-                          const int32_t* seg_flags, const float* g, float grad_scale, float* blk_part,
-                          fpnmt_stream_t stream) {
+static int grad_sumsq_launch(int blk_first, int nblocks, int max_grid, const int32_t* blk_seg,
+                             const long long* blk_start, int block_elems, const long long* off,
+                             const int32_t* seg_flags, const fpnmt_seg_group* groups, const float* g,
+                             float grad_scale, float* blk_part, fpnmt_stream_t stream) {
   if (nblocks <= 0) return 0;
   if (!blk_part) return fail(FPNMT_E_ARG, "grad_sumsq: null partials");
   if (blk_first < 0 || max_grid < 0) return fail(FPNMT_E_ARG, "grad_sumsq: negative first block / grid");
   const int grid = max_grid > 0 ? std::min(nblocks, max_grid) : nblocks;
-  hipLaunchKernelGGL(sumsq_kernel, dim3(grid), dim3(256), 0, S(stream), blk_first, nblocks, blk_seg, blk_start,
-                     block_elems, off, seg_flags, g, grad_scale, blk_part);
+  if (groups)
+    hipLaunchKernelGGL(sumsq_kernel<true>, dim3(grid), dim3(256), 0, S(stream), blk_first, nblocks, blk_seg,
+                       blk_start, block_elems, off, seg_flags, groups, g, grad_scale, blk_part);
+  else
+    hipLaunchKernelGGL(sumsq_kernel<false>, dim3(grid), dim3(256), 0, S(stream), blk_first, nblocks, blk_seg,
+                       blk_start, block_elems, off, seg_flags, (const fpnmt_seg_group*)nullptr, g, grad_scale,
+                       blk_part);
   return check_launch("grad_sumsq");
+}
+
+int fpnmt_grad_sumsq_part(int blk_first, int nblocks, int max_grid, const int32_t* blk_seg,
+                          const long long* blk_start, int block_elems, const long long* off,
+                          const int32_t* seg_flags, const float* g, float grad_scale, float* blk_part,
+                          fpnmt_stream_t stream) {
+  return grad_sumsq_launch(blk_first, nblocks, max_grid, blk_seg, blk_start, block_elems, off, seg_flags, nullptr, g,
+                           grad_scale, blk_part, stream);
+}
+
+int fpnmt_grad_sumsq_groups(int blk_first, int nblocks, int max_grid, const int32_t* blk_seg,
+                            const long long* blk_start, int block_elems, const long long* off,
+                            const int32_t* seg_flags, const fpnmt_seg_group* groups, const float* g,
+                            float grad_scale, float* blk_part, fpnmt_stream_t stream) {
+  if (!groups) return fail(FPNMT_E_ARG, "grad_sumsq_groups: null group table");
+  return grad_sumsq_launch(blk_first, nblocks, max_grid, blk_seg, blk_start, block_elems, off, seg_flags, groups, g,
+                           grad_scale, blk_part, stream);
 }
 
 int fpnmt_grad_sumsq(int nblocks, const int32_t* blk_seg, const long long* blk_start, int block_elems,
@@ -447,12 +497,12 @@ int fpnmt_grad_sumsq(int nblocks, const int32_t* blk_seg, const long long* blk_s
                                blk_part, stream);
 }
 
-int fpnmt_amsgrad_step_part(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
-                            const int32_t* blk_seg, const long long* blk_start, int block_elems,
-                            const long long* off, const int32_t* seg_flags, float* param, const float* grad,
-                            float* m, float* v, float* vhat, const float* sumsq, const float* blk_part,
-                            const int32_t* seg_blk0, long long* step, const fpnmt_seg_prep* preps,
-                            fpnmt_stream_t stream) {
+static int amsgrad_launch(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
+                          const int32_t* blk_seg, const long long* blk_start, int block_elems,
+                          const long long* off, const int32_t* seg_flags, float* param, const float* grad,
+                          float* m, float* v, float* vhat, const float* sumsq, const float* blk_part,
+                          const int32_t* seg_blk0, long long* step, const fpnmt_seg_prep* preps,
+                          const fpnmt_seg_group* groups, fpnmt_stream_t stream) {
   if (!d || !step) return fail(FPNMT_E_ARG, "amsgrad: null");
   if (blk_first < 0 || max_grid < 0) return fail(FPNMT_E_ARG, "amsgrad: negative first block / grid");
   const int grid = max_grid > 0 ? std::min(nblocks, max_grid) : nblocks;
@@ -461,17 +511,41 @@ int fpnmt_amsgrad_step_part(const fpnmt_adam_desc* d, int blk_first, int nblocks
   if (preps && (!seg_blk0 || block_elems > 16384 || block_elems % 4096))
     return fail(FPNMT_E_ARG, "amsgrad_prep: needs seg_blk0 and block_elems a multiple of 4096 (<= 16384)");
   if (nblocks > 0) {
-    if (preps)
-      hipLaunchKernelGGL(amsgrad_kernel<true>, dim3(grid), dim3(256), 0, S(stream), *d, blk_first, nblocks, blk_seg,
-                         blk_start, block_elems, off, seg_flags, param, grad, m, v, vhat, sumsq, blk_part, seg_blk0,
-                         step, preps);
-    else
-      hipLaunchKernelGGL(amsgrad_kernel<false>, dim3(grid), dim3(256), 0, S(stream), *d, blk_first, nblocks, blk_seg,
-                         blk_start, block_elems, off, seg_flags, param, grad, m, v, vhat, sumsq, blk_part, seg_blk0,
-                         step, (const fpnmt_seg_prep*)nullptr);
+#define FPNMT_AMSGRAD_LAUNCH(PREP, GROUPS)                                                                       \
+  hipLaunchKernelGGL((amsgrad_kernel<PREP, GROUPS>), dim3(grid), dim3(256), 0, S(stream), *d, blk_first, nblocks, \
+                     blk_seg, blk_start, block_elems, off, seg_flags, param, grad, m, v, vhat, sumsq, blk_part,   \
+                     seg_blk0, step, PREP ? preps : (const fpnmt_seg_prep*)nullptr,                               \
+                     GROUPS ? groups : (const fpnmt_seg_group*)nullptr)
+    if (groups) {
+      if (preps) FPNMT_AMSGRAD_LAUNCH(true, true); else FPNMT_AMSGRAD_LAUNCH(false, true);
+    } else {
+      if (preps) FPNMT_AMSGRAD_LAUNCH(true, false); else FPNMT_AMSGRAD_LAUNCH(false, false);
+    }
+#undef FPNMT_AMSGRAD_LAUNCH
   }
   if (inc_step) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, S(stream), step);
   return check_launch("amsgrad");
+}
+
+int fpnmt_amsgrad_step_part(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
+                            const int32_t* blk_seg, const long long* blk_start, int block_elems,
+                            const long long* off, const int32_t* seg_flags, float* param, const float* grad,
+                            float* m, float* v, float* vhat, const float* sumsq, const float* blk_part,
+                            const int32_t* seg_blk0, long long* step, const fpnmt_seg_prep* preps,
+                            fpnmt_stream_t stream) {
+  return amsgrad_launch(d, blk_first, nblocks, inc_step, max_grid, blk_seg, blk_start, block_elems, off, seg_flags,
+                        param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, nullptr, stream);
+}
+
+int fpnmt_amsgrad_step_groups(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
+                              const int32_t* blk_seg, const long long* blk_start, int block_elems,
+                              const long long* off, const int32_t* seg_flags, float* param, const float* grad,
+                              float* m, float* v, float* vhat, const float* sumsq, const float* blk_part,
+                              const int32_t* seg_blk0, long long* step, const fpnmt_seg_prep* preps,
+                              const fpnmt_seg_group* groups, fpnmt_stream_t stream) {
+  if (!groups) return fail(FPNMT_E_ARG, "amsgrad_step_groups: null group table");
+  return amsgrad_launch(d, blk_first, nblocks, inc_step, max_grid, blk_seg, blk_start, block_elems, off, seg_flags,
+                        param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, groups, stream);
 }
 
 int fpnmt_amsgrad_step_prep(const fpnmt_adam_desc* d, int nblocks, const int32_t* blk_seg,

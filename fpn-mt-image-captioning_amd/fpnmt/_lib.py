@@ -137,6 +137,10 @@ class SegPrep(C.Structure):
     ]
 
 
+class SegGroup(C.Structure):
+    _fields_ = [("lr_scale", C.c_float), ("weight_decay", C.c_float), ("frozen", C.c_int32), ("reserved", C.c_int32)]
+
+
 P = C.c_void_p
 I = C.c_int
 LL = C.c_longlong
@@ -216,6 +220,9 @@ SIGNATURES = {
     "fpnmt_amsgrad_step_prep": [C.POINTER(AdamDesc), I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "fpnmt_grad_sumsq_part": [I, I, I, P, P, I, P, P, P, F, P, P],
     "fpnmt_amsgrad_step_part": [C.POINTER(AdamDesc), I, I, I, I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P],
+    "fpnmt_grad_sumsq_groups": [I, I, I, P, P, I, P, P, P, P, F, P, P],
+    "fpnmt_amsgrad_step_groups": [C.POINTER(AdamDesc), I, I, I, I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                  P],
     "fpnmt_decode_attention": [I, I, I, I, I, F, P, LL, P, LL, LL, LL, LL, P, I, I, P, LL, P],
     "fpnmt_beam_step": [I, I, I, P, LL, P, P, P, I, I, P, P, I, I, P, P, I, P, P, P],
     "fpnmt_beam_step_log": [I, I, I, P, LL, P, P, P, P, P, I, I, P, P, I, I, P, P, P],

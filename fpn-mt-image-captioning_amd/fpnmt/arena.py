@@ -23,6 +23,65 @@ ALIGN = 64  # elements (256 B) per segment start: keeps 16-B vector loads aligne
 BLOCK_ELEMS = 16384
 
 
+class SegGroups:
+    """The per-segment fpnmt_seg_group device table of an arena (lr_scale,
+    weight_decay, frozen) and its host mirror. The table is allocated once
+    and only ever written in place (stream-ordered): captured optimizer
+    graphs hold its pointer and read the values of the moment they replay."""
+
+    def __init__(self, arena, rows):
+        """rows: per segment (group index, lr_scale, weight_decay, frozen),
+        as fpnmt.param_groups.assign returns them."""
+        n = len(arena.params)
+        if len(rows) != n:
+            raise ValueError(f"SegGroups: {len(rows)} rows for {n} segments")
+        self.group_of = [int(r[0]) for r in rows]
+        self.lr_scale = [float(r[1]) for r in rows]
+        self.weight_decay = [float(r[2]) for r in rows]
+        self.frozen = [bool(r[3]) for r in rows]
+        tab = (L.SegGroup * max(1, n))()
+        for e, s, w, f in zip(tab, self.lr_scale, self.weight_decay, self.frozen):
+            e.lr_scale, e.weight_decay, e.frozen = s, w, int(f)
+        raw = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.int32).view(-1, 4)
+        self.table = raw.to(arena.device)  # (nseg, 4) int32: float bits, float bits, flag, 0
+        self._f32 = self.table.view(torch.float32)
+        self._blk_seg = arena._blk_seg_host
+
+    def _write(self, col, segs, values):
+        if not segs:
+            return
+        dev = self.table.device
+        idx = torch.tensor(segs, dtype=torch.int64).to(dev)
+        if col == 2:
+            self.table[:, 2].index_copy_(0, idx, torch.tensor(values, dtype=torch.int32).to(dev))
+        else:
+            self._f32[:, col].index_copy_(0, idx, torch.tensor(values, dtype=torch.float32).to(dev))
+
+    def set_lr_scale(self, segs, values):
+        for i, v in zip(segs, values):
+            self.lr_scale[i] = float(v)
+        self._write(0, list(segs), [float(v) for v in values])
+
+    def set_weight_decay(self, segs, values):
+        for i, v in zip(segs, values):
+            self.weight_decay[i] = float(v)
+        self._write(1, list(segs), [float(v) for v in values])
+
+    def set_frozen(self, segs, flag):
+        for i in segs:
+            self.frozen[i] = bool(flag)
+        self._write(2, list(segs), [int(bool(flag))] * len(segs))
+
+    def trim(self, b0, b1):
+        """[b0, b1) without its leading and trailing blocks of frozen
+        segments (workgroups that would only exit are not launched)."""
+        while b0 < b1 and self.frozen[self._blk_seg[b0]]:
+            b0 += 1
+        while b1 > b0 and self.frozen[self._blk_seg[b1 - 1]]:
+            b1 -= 1
+        return b0, b1
+
+
 class ParamArena:
     def __init__(self, params, device, sparse_names=()):
         """params: ordered list of (name, nn.Parameter) — shared parameters
@@ -75,6 +134,7 @@ class ParamArena:
                 blk_start.append(s)
                 s += BLOCK_ELEMS
         self.nblocks = len(blk_seg)
+        self._blk_seg_host = list(blk_seg)
         # first block of every segment (blocks are in segment order): the
         # optimizer sums a segment's per-block norm partials in block order
         seg_blk0, b = [], 0
@@ -133,14 +193,18 @@ class ParamArena:
         return self._seg_blk0_host[i]
 
     def amsgrad_step(self, lr_schedule, beta1=0.9, beta2=0.98, eps=1e-9, clipnorm=1.0, grad_scale=1.0,
-                     preps=None, blocks=None, inc_step=True, max_grid=0):
+                     preps=None, blocks=None, inc_step=True, max_grid=0, groups=None):
         """Keras AMSGrad + per-tensor clip_by_norm over the arena. preps: a
         device table of fpnmt_seg_prep (one per segment, layers.FusedPrep)
         whose non-null entries get their bf16 compute copies written by the
         same kernel. blocks: (first, end) block range of whole segments (one
         part of a step updated in parts); inc_step: advance `iterations`
         (only the step's last part); max_grid: at most that many workgroups
-        striding over the range (0: one per block)."""
+        striding over the range (0: one per block). groups: a SegGroups of
+        this arena (make_groups): the step through fpnmt_amsgrad_step_groups
+        with its per-segment rate scale, decoupled weight decay and frozen
+        flags; frozen segments at either end of the range are not launched.
+        None: the plain entry points, as before."""
         d = L.AdamDesc()
         d.beta1, d.beta2, d.eps, d.clipnorm = beta1, beta2, eps, clipnorm
         d.grad_scale = grad_scale
@@ -154,6 +218,19 @@ class ParamArena:
             d.sched_warm_pow = float(lr_schedule.warmup_steps ** -1.5)
         b0, b1 = (0, self.nblocks) if blocks is None else blocks
         s = L.stream_ptr()
+        if groups is not None:
+            b0, b1 = groups.trim(b0, b1)
+            gt = L.ptr(groups.table)
+            if clipnorm > 0 and b1 > b0:
+                L.call("fpnmt_grad_sumsq_groups", b0, b1 - b0, max_grid, L.ptr(self.blk_seg), L.ptr(self.blk_start),
+                       BLOCK_ELEMS, L.ptr(self.seg_bounds), L.ptr(self.seg_flags), gt, L.ptr(self.grad), grad_scale,
+                       L.ptr(self.blk_part), s)
+            L.call("fpnmt_amsgrad_step_groups", d, b0, b1 - b0, 1 if inc_step else 0, max_grid, L.ptr(self.blk_seg),
+                   L.ptr(self.blk_start), BLOCK_ELEMS, L.ptr(self.seg_bounds), L.ptr(self.seg_flags),
+                   L.ptr(self.flat), L.ptr(self.grad), L.ptr(self.m), L.ptr(self.v), L.ptr(self.vhat),
+                   L.ptr(self.sumsq), L.ptr(self.blk_part), L.ptr(self.seg_blk0), L.ptr(self.step),
+                   L.ptr(preps) if preps is not None else None, gt, s)
+            return
         if clipnorm > 0 and b1 > b0:  # clipnorm 0: no clip_by_norm, no norms needed
             L.call("fpnmt_grad_sumsq_part", b0, b1 - b0, max_grid, L.ptr(self.blk_seg), L.ptr(self.blk_start), BLOCK_ELEMS,
                    L.ptr(self.seg_bounds), L.ptr(self.seg_flags), L.ptr(self.grad), grad_scale,
@@ -163,6 +240,11 @@ class ParamArena:
                L.ptr(self.grad), L.ptr(self.m), L.ptr(self.v), L.ptr(self.vhat), L.ptr(self.sumsq),
                L.ptr(self.blk_part), L.ptr(self.seg_blk0), L.ptr(self.step),
                L.ptr(preps) if preps is not None else None, s)
+
+    def make_groups(self, rows):
+        """A SegGroups table for this arena from per-segment (group index,
+        lr_scale, weight_decay, frozen) rows (fpnmt.param_groups.assign)."""
+        return SegGroups(self, rows)
 
     # ------------------------------------------------------ compute copies
     def register_preparer(self, fn):

@@ -1782,10 +1782,12 @@ class LayerNormViewsFn(torch.autograd.Function):
     the shared LayerNormalization, + pe[:L_i], Dropout) for all views as ONE
     launch per pass (fpnmt_layernorm_views_fwd / _bwd); the same rows, masks
     (seeds drawn in view order) and per-view gamma / beta sums as one
-    LayerNormFn + DropoutFn per view."""
+    LayerNormFn + DropoutFn per view. _anchor = layer.gamma: a tensor input
+    that requires grad, so the node (and with it gamma's and beta's gradient)
+    exists when no view does: a frozen feature extractor's outputs."""
 
     @staticmethod
-    def forward(ctx, layer, pe, drop_p, *xs):
+    def forward(ctx, layer, pe, drop_p, _anchor, *xs):
         xs = [x.contiguous() for x in xs]
         n, d = len(xs), xs[0].shape[-1]
         tab = (L.LnView * n)()
@@ -1831,7 +1833,7 @@ class LayerNormViewsFn(torch.autograd.Function):
             keep.append(dy)
         call("fpnmt_layernorm_views_bwd", dtype_code(xs[0].dtype), n, d, tab, ptr(layer.gamma), ctx.p, ptr(ctx.st),
              ptr(_grad_of(layer.gamma)), ptr(_grad_of(layer.beta)), stream_ptr())
-        return (None, None, None, *dxs)
+        return (None, None, None, None, *dxs)
 
 
 # --------------------------------------------- one-key cross-attention

@@ -53,13 +53,23 @@ from . import layers as flayers
 from . import ops
 from .arena import ParamArena
 from .layers import group_param_order
+from . import param_groups as pgroups
 
 
 class TrainEngine:
     def __init__(self, transformer, schedule, beta1=0.9, beta2=0.98, eps=1e-9, clipnorm=1.0, use_graph=True,
                  group=None, bucket_bytes=fdist.DEFAULT_BUCKET_BYTES, split_backward=None, bucket_dtype=None,
-                 sync_bn=True, label_smoothing=0.0):
+                 sync_bn=True, label_smoothing=0.0, param_groups=None):
+        """param_groups: None runs the plain step (every trainable tensor at
+        the schedule's rate, no decay: the reference's optimizer). A list of
+        fpnmt.param_groups.ParamGroup (an empty one included) runs the same
+        step through fpnmt_amsgrad_step_groups with a per-segment rate scale,
+        decoupled weight decay and frozen flags. Every tensor that is
+        trainable at construction stays in the arena, frozen ones included:
+        optimizer state and checkpoints keep one layout across phases, and
+        set_lr_scale / set_weight_decay / set_frozen change a group later."""
         from models.transformer import create_masks  # noqa: F401 (ensures import path)
+        groups_in = pgroups.validate(param_groups) if param_groups is not None else None
         if not 0.0 <= float(label_smoothing) < 1.0:  # NaN fails both comparisons
             raise ValueError(f"TrainEngine: label_smoothing must lie in [0, 1), got {label_smoothing!r}")
         self.label_smoothing = float(label_smoothing)
@@ -113,6 +123,17 @@ class TrainEngine:
         transformer.decoder.embedding.sumsq_slot = self.arena.sumsq_slot(emb)
         self.emb_seg = self.arena.seg_of(emb)
         ops.runtime.seed_tensor = self.arena.step
+        # parameter groups: the device table is built once (captured graphs
+        # hold its pointer); frozen groups lose requires_grad, so autograd
+        # prunes their backward, and keep their arena segments
+        self.param_groups = groups_in
+        self.seg_groups = None
+        transformer.encoder.feature_extractor.freeze_backbone_bn = False
+        if groups_in is not None:
+            rows = pgroups.assign(self.arena.names, self.arena.params, groups_in)
+            self.seg_groups = self.arena.make_groups(rows)
+            self._check_frozen_set()
+            self._apply_frozen()
         # opt-in low-precision buckets: one preallocated staging copy of the
         # gradient arena; each range is cast into it at the end of the graph
         # that produced it and the reduced sum is cast back at the start of the
@@ -149,6 +170,119 @@ class TrainEngine:
         self._esteps = {}  # eval_step: shapes -> [calls, graph, static inputs, outputs]
         self._eval_gen = -1  # the compute copies' generation the eval graphs last saw
         self.eval_totals = torch.zeros(3, dtype=torch.float64, device=dev)  # eval_step(accumulate=True)
+
+    # ------------------------------------------------------ parameter groups
+    _frozen_layers = {}  # id -> weight layer whose kernel is frozen (their compute copies need no refresh)
+
+    def _group_segs(self, name):
+        """Arena segments of the group `name` ("default": the unmatched ones)."""
+        if self.seg_groups is None:
+            raise ValueError("TrainEngine was built without param_groups")
+        names = [g.name for g in self.param_groups]
+        if name in names:
+            gi = names.index(name)
+        elif name == pgroups.DEFAULT_NAME:
+            gi = -1
+        else:
+            raise ValueError(f"no parameter group {name!r}; groups: {names + [pgroups.DEFAULT_NAME]}")
+        return [i for i, g in enumerate(self.seg_groups.group_of) if g == gi]
+
+    def _check_frozen_set(self, frozen=None):
+        """What can be frozen: nothing, the backbone, or the whole feature
+        extractor. The pruning rests on autograd never reaching a frozen
+        tensor, which holds for those two sets (the backbone is the model's
+        first stage, the extractor its first two); the transformer's fused
+        Functions always write their weight gradients, and a trainable layer
+        behind an identity shortcut of frozen ones would get no gradient."""
+        frozen = self.seg_groups.frozen if frozen is None else frozen
+        names = self.arena.names
+        got = {names[i] for i, f in enumerate(frozen) if f}
+        if not got:
+            return
+        bb = {n for n in names if n.startswith(pgroups.backbone_prefixes(self.model))}
+        fe = {n for n in names if n.startswith(pgroups.FE_PREFIX)}
+        if got != bb and got != fe:
+            odd = sorted(got - fe) or sorted(got ^ bb)
+            raise ValueError("TrainEngine: frozen groups must cover exactly the backbone or the whole feature "
+                             f"extractor (param_groups.backbone_group / feature_extractor_group); e.g. {odd[:3]}")
+
+    def _apply_frozen(self):
+        """requires_grad of every arena parameter from the frozen flags, the
+        backbone's BatchNorm mode, and the set of frozen weight layers."""
+        sg = self.seg_groups
+        for p, f in zip(self.arena.params, sg.frozen):
+            p.requires_grad_(not f)
+        fe = self.model.encoder.feature_extractor
+        bbp = pgroups.backbone_prefixes(self.model)
+        # a frozen backbone's BatchNorm (MobileNetV2) runs in inference mode:
+        # no moving-statistics update, no SyncBN collective
+        fe.freeze_backbone_bn = any(f for n, f in zip(self.arena.names, sg.frozen) if n.startswith(bbp))
+        self._frozen_layers = {id(m): m for m in flayers.weight_layers(self.model)
+                               if id(m.kernel) in self.arena.index and sg.frozen[self.arena.index[id(m.kernel)]]}
+        self._range_frozen_cache = {}
+
+    def _range_frozen(self, part):
+        """Every segment of exchange range `part` is frozen (an empty range is not)."""
+        if self.seg_groups is None:
+            return False
+        hit = self._range_frozen_cache.get(part)
+        if hit is None:
+            a, b = self.ranges[part]
+            segs = [i for i, o in enumerate(self.arena.offsets) if a <= o < b]
+            hit = self._range_frozen_cache[part] = bool(segs) and all(self.seg_groups.frozen[i] for i in segs)
+        return hit
+
+    def _refresh_frozen_copies(self):
+        """Before a capture or a replay: frozen layers are left out of the
+        step's compute-copy refresh, so copies made stale since
+        (layers.invalidate_weights(): a hand edit, a precision change) are
+        rebuilt here, outside the graph."""
+        if any(m._gen != flayers._GEN[0] for m in self._frozen_layers.values()):
+            flayers.prepare_all(self.model, fpnmt.compute_dtype())
+
+    def set_lr_scale(self, name, s):
+        """Group `name` trains at s times the schedule's rate from the next
+        step on. Written into the device table in place (stream-ordered): the
+        captured graphs are kept and the next replay reads the new value."""
+        s = pgroups._finite_nonneg(s, f"set_lr_scale({name!r})")
+        segs = self._group_segs(name)
+        self.seg_groups.set_lr_scale(segs, [s] * len(segs))
+
+    def set_weight_decay(self, name, w):
+        """Group `name` decays with coefficient w (a number, or a callable
+        (name, param) -> number such as param_groups.decay_matrices(0.01))
+        from the next step on; in place, no recapture, like set_lr_scale."""
+        segs = self._group_segs(name)
+        vals = [pgroups.decay_of(w, self.arena.names[i], self.arena.params[i], f"set_weight_decay({name!r})")
+                for i in segs]
+        self.seg_groups.set_weight_decay(segs, vals)
+
+    def set_frozen(self, name, flag):
+        """Freeze (flag True) or unfreeze group `name`: flips requires_grad on
+        its parameters, so the backward no longer visits them (pruned, not
+        masked), and the frozen flag of their segments in the device table.
+        The captured step graphs (step, step_weighted, the split sequence) are
+        dropped, since the autograd graph they recorded changed: the next
+        call at a shape runs eagerly and the one after captures, as at
+        start-up. Eval graphs are kept. Optimizer state is kept too: a frozen
+        group's m, v and vhat stay as they are, and after unfreezing it
+        continues from them with the global step counter (its bias correction
+        is that of the current step, not of the steps it took part in)."""
+        segs = self._group_segs(name)
+        flag = bool(flag)
+        new = list(self.seg_groups.frozen)
+        for i in segs:
+            new[i] = flag
+        self._check_frozen_set(new)
+        if new == self.seg_groups.frozen:
+            return
+        self.seg_groups.set_frozen(segs, flag)
+        self._apply_frozen()
+        self.calls = 0
+        self.graphs = None
+        self.static = None
+        self._wsteps = {}
+        flayers.invalidate_weights()  # an unfrozen layer comes back into the refresh
 
     # ------------------------------------------------------------ pieces
     def _one(self, loss):
@@ -236,7 +370,7 @@ class TrainEngine:
             # every CU slot until it drained (profiles/r05/early_update_r5h.txt)
             self.arena.amsgrad_step(self.schedule, grad_scale=1.0 / self.world, preps=None,
                                     blocks=(0, self.early_blocks), inc_step=False,
-                                    max_grid=fpnmt.config.early_update_grid, **self.adam)
+                                    max_grid=fpnmt.config.early_update_grid, groups=self.seg_groups, **self.adam)
         self._early_pending = True
 
     def _fwd_bwd_split(self, img, tok, weights=None):
@@ -306,6 +440,8 @@ class TrainEngine:
         extra = [self.arena.sumsq[self.emb_seg:self.emb_seg + 1]] if part in (None, 0) else None
         if rng[1] <= rng[0]:
             return []
+        if part is not None and self._range_frozen(part):
+            return []  # nothing in the range is trained: no gradient, no exchange
         staging = self.low[rng[0]:rng[1]] if self.low is not None else None
         return fdist.allreduce_flat(g[rng[0]:rng[1]], self.bucket_bytes, self.group, extra=extra, wait=wait,
                                     bucket_dtype=self.bucket_dtype, staging=staging)
@@ -327,7 +463,10 @@ class TrainEngine:
                 skip = {id(m) for m in fp._mods
                         if self.arena.offsets[self.arena.index[id(m.kernel)]] >= self.split_at}
         self.arena.amsgrad_step(self.schedule, grad_scale=1.0 / self.world, preps=fp.table if fp else None,
-                                blocks=blocks, **self.adam)
+                                blocks=blocks, groups=self.seg_groups, **self.adam)
+        if self._frozen_layers:
+            # frozen masters do not change: their (fresh) copies need no refresh
+            skip = set(skip) | {i for i, m in self._frozen_layers.items() if m._gen == flayers._GEN[0]}
         flayers.prepare_all(self.model, skip=skip)
         if fp:
             fp.mark_fresh()
@@ -339,6 +478,8 @@ class TrainEngine:
             self._bwd_encoder()
             works += self._exchange(1, wait=False)
             for i in range(len(self._stages)):
+                if self._range_frozen(2 + i):
+                    continue
                 self._bwd_stage(i)
                 works += self._exchange(2 + i, wait=False)
             for w in works:
@@ -373,6 +514,7 @@ class TrainEngine:
             import fpnmt
             flayers.prepare_all(self.model, fpnmt.compute_dtype())
             return self._eager(img, tok)
+        self._refresh_frozen_copies()
         if self.graphs is None:
             self._capture(img, tok)
         if img.shape != self.static[0].shape or tok.shape != self.static[1].shape:
@@ -410,6 +552,7 @@ class TrainEngine:
         if not self.use_graph or ent[0] == 1:
             flayers.prepare_all(self.model, fpnmt.compute_dtype())
             return self._eager(img, tok, weights)
+        self._refresh_frozen_copies()
         if ent[1] is None:
             ent[1], ent[2] = self._capture(img, tok, weights)
         graphs, static = ent[1], ent[2]
@@ -501,6 +644,8 @@ class TrainEngine:
                 tl.graph("G2")
                 tl.exchange(1, w)
             for i, g in enumerate(gs):
+                if g is None:  # a stage whose parameters are all frozen: no backward, no exchange
+                    continue
                 g.replay()
                 w = self._exchange(2 + i, wait=False)
                 works += w
@@ -535,8 +680,13 @@ class TrainEngine:
             def g1():
                 out["loss"] = self._fwd_bwd_split(s_img, s_tok, s_w).detach()
             n = len(self.model.encoder.feature_extractor.stage_prefixes())
-            stage_fns = [(lambda i=i: self._bwd_stage(i)) for i in range(n)]
-            graphs = capture_sequence([g1, self._bwd_encoder] + stage_fns + [self._update])
+            live = [i for i in range(n) if not self._range_frozen(2 + i)]
+            stage_fns = [(lambda i=i: self._bwd_stage(i)) for i in live]
+            got = capture_sequence([g1, self._bwd_encoder] + stage_fns + [self._update])
+            stage_graphs = [None] * n  # a wholly frozen stage has no graph
+            for i, g in zip(live, got[2:-1]):
+                stage_graphs[i] = g
+            graphs = got[:2] + stage_graphs + got[-1:]
         elif self.world == 1:
             def g():
                 out["loss"] = self._fwd_bwd(s_img, s_tok, s_w).detach()

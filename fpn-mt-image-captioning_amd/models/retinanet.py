@@ -218,10 +218,14 @@ class FeatureExtractor(nn.Module):
         return [self.HEAD_PREFIXES, ["retinanet_model.fpn."]] + [[bb + p for p in segs[i][1]]
                                                                   for i in reversed(range(len(segs)))]
 
+    # set by TrainEngine while the backbone's parameter group is frozen: its
+    # BatchNorm then normalises with the moving statistics in a train step too
+    freeze_backbone_bn = False
+
     def set_training(self, training=None):
         bb = self.retinanet_model.backbone
         if hasattr(bb, "bn_training"):
-            bb.bn_training = self.training if training is None else bool(training)
+            bb.bn_training = (self.training if training is None else bool(training)) and not self.freeze_backbone_bn
 
     def staged(self, inp, training=None):
         """forward() cut at the backbone taps and the pyramid: returns

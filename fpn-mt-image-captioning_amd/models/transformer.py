@@ -254,7 +254,7 @@ class Encoder(nn.Module):
         if fpnmt.config.fuse_view_norms:
             # every view's LN, += pe[:seq_len], dropout: one launch per pass
             x = list(ops.LayerNormViewsFn.apply(self.layernorm1, self.pos_encoding,
-                                                self.rate if training else 0.0, *x))
+                                                self.rate if training else 0.0, self.layernorm1.gamma, *x))
         else:
             for i_x in range(NUM_OF_PYRAMIDS):
                 _x = self.layernorm1(x[i_x], pe=self.pos_encoding)  # LN, then += pe[:seq_len]

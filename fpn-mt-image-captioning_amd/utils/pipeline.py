@@ -26,6 +26,7 @@ from common.common_definitions import (BEAM_SEARCH_N, CLIPNORM_MODE, DATADIR, DA
 import fpnmt
 from fpnmt import ops
 from fpnmt.checkpoint import Checkpoint, CheckpointManager
+from fpnmt.param_groups import recipe_groups
 from fpnmt.train import TrainEngine
 from models.transformer import Transformer, create_look_ahead_mask
 from utils.utils import CustomSchedule, Mean, SmartCheckpointSaver
@@ -55,7 +56,16 @@ class Pipeline:
     def __init__(self, tokenizer_filename=None, checkpoint_path=None, max_seq_len=32, target_vocab_size=None,
                  image_size=IMAGE_INPUT_SIZE, n_layers=num_layers, backbone=None, rate=DROPOUT_RATE,
                  device="cuda", init=None, use_graph=True, clipnorm_mode=CLIPNORM_MODE, max_to_keep=100,
-                 data_dir=DATADIR, data_type_val=DATATYPE_VAL, label_smoothing=0.0):
+                 data_dir=DATADIR, data_type_val=DATATYPE_VAL, label_smoothing=0.0, param_groups=None,
+                 backbone_lr_scale=1.0, freeze=(), weight_decay=0.0):
+        """param_groups (a list of fpnmt.param_groups.ParamGroup), or the
+        common cases by keyword: backbone_lr_scale (the CNN backbone at that
+        fraction of the transformer's rate), freeze (a subset of {"backbone",
+        "feature_extractor"}), weight_decay (decoupled, on matrices only).
+        The keywords build the groups "backbone", "feature_extractor" (the
+        FPN and heads) and "transformer", whose values
+        engine.set_lr_scale / set_weight_decay / set_frozen change later. Not
+        in the reference; at the defaults the step is the reference's."""
         self.max_seq_len = max_seq_len
         self._metric_eval_src = (data_dir, data_type_val)
         self._metric_eval = None
@@ -73,9 +83,13 @@ class Pipeline:
         self.transformer = Transformer(n_layers, d_model, num_heads, dff, input_vocab_size, self.target_vocab_size,
                                        rate, max_seq_len=self.max_seq_len, backbone=backbone, init=init).to(device)
         self.learning_rate = CustomSchedule(dff, WARM_UP_STEPS)  # pipeline.py:29 (d_model arg = dff)
+        recipe = recipe_groups(self.transformer, backbone_lr_scale, freeze, weight_decay)
+        if param_groups is not None and recipe is not None:
+            raise ValueError("Pipeline: give param_groups or backbone_lr_scale / freeze / weight_decay, not both")
         self.engine = TrainEngine(self.transformer, self.learning_rate, beta1=0.9, beta2=0.98, eps=1e-9,
                                   clipnorm=clipnorm_for(clipnorm_mode), use_graph=use_graph,
-                                  label_smoothing=label_smoothing)  # not in the reference; 0: its one-hot loss
+                                  label_smoothing=label_smoothing,  # not in the reference; 0: its one-hot loss
+                                  param_groups=param_groups if param_groups is not None else recipe)
         self.optimizer = self.engine
         self.train_loss = Mean(name="train_loss")  # pipeline.py:35
         self.checkpoint_path = checkpoint_path

@@ -756,6 +756,40 @@ int fpnmt_amsgrad_step_part(const fpnmt_adam_desc* d, int blk_first, int nblocks
                             const float* grad, float* m, float* v, float* vhat, const float* sumsq,
                             const float* blk_part, const int32_t* seg_blk0, long long* step,
                             const fpnmt_seg_prep* preps, fpnmt_stream_t stream);
+/* Parameter groups: the block-range forms with a per-segment device table
+ * groups[i] (one 16-B entry per segment, read once per block like preps[i];
+ * no per-element load is added). For a segment that is not frozen, per
+ * element in fp32, with lr, alpha, m, v, vhat as in the plain step,
+ * s = lr_scale, w = weight_decay:
+ *   p_new = (p - (m_new * (alpha * s)) / (sqrtf(vhat_new) + eps)) - (lr * s * w) * p
+ * (decoupled, AdamW-style decay on the old p; the term is not evaluated at
+ * w == 0, and s == 1, w == 0 gives fpnmt_amsgrad_step_part's result bit for
+ * bit). s == 0 is legal: m, v, vhat advance and p only decays. Clipping stays
+ * per tensor and comes first; seg_flags keep their meaning.
+ * frozen != 0: the segment's blocks return before any load: its grad is
+ * never read, its param, m, v, vhat, norm partials and compute copies
+ * (preps) are never written. A caller that knows frozen segments at the head
+ * or tail of a range should not launch their blocks at all. The table is
+ * read at execution time: values written into it (stream-ordered) between
+ * two replays of a captured launch take effect at the next replay.
+ * FPNMT_E_ARG: groups null, otherwise as fpnmt_amsgrad_step_part.          */
+typedef struct fpnmt_seg_group {
+  float lr_scale;
+  float weight_decay;
+  int32_t frozen;
+  int32_t reserved;
+} fpnmt_seg_group;
+int fpnmt_grad_sumsq_groups(int blk_first, int nblocks, int max_grid, const int32_t* blk_seg,
+                            const long long* blk_start, int block_elems, const long long* off,
+                            const int32_t* seg_flags, const fpnmt_seg_group* groups, const float* g,
+                            float grad_scale, float* blk_part, fpnmt_stream_t stream);
+int fpnmt_amsgrad_step_groups(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
+                              const int32_t* blk_seg, const long long* blk_start, int block_elems,
+                              const long long* off, const int32_t* seg_flags, float* param,
+                              const float* grad, float* m, float* v, float* vhat, const float* sumsq,
+                              const float* blk_part, const int32_t* seg_blk0, long long* step,
+                              const fpnmt_seg_prep* preps, const fpnmt_seg_group* groups,
+                              fpnmt_stream_t stream);
 
 /* ---- batched beam decode (BASELINE C5; utils/pipeline.py:82-154) --------
  * fpnmt_decode_attention: softmax(q k^T * scale) v for ONE query position per

@@ -1,0 +1,117 @@
+"""The C2 training step of bench.py (same model, shapes, seed and synthetic
+batch; imported from it, bench.py is not edited) under four parameter-group
+settings:
+
+  a  no groups (param_groups=None: the plain step)
+  b  all trainable, backbone lr_scale 0.1, weight decay 0.01 on matrices
+  c  backbone frozen
+  d  feature extractor frozen
+
+One engine per setting is built and warmed up (eager call, capture, replays),
+then the settings are timed in turn, `--rounds` times over, each window
+`--steps` graph replays between two device events (>= 1 s at the default):
+the spread of a setting over the rounds is printed next to the differences
+between settings. Prints one JSON line.
+
+  python tools/bench_param_groups.py [--settings abcd] [--steps 150] [--rounds 3]
+  rocprofv3 --kernel-trace --stats -d DIR -o NAME --output-format csv -- \\
+      python tools/bench_param_groups.py --settings c --steps 20 --rounds 1
+(then tools/step_counts.py / tools/step_breakdown.py on the kernel trace give
+the kernels per step and the optimizer's and the reductions' share)."""
+import argparse
+import json
+import math
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "fpn-mt-image-captioning_amd"), ROOT):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def groups_for(setting, model):
+    from fpnmt import param_groups as G
+    if setting == "a":
+        return None
+    if setting == "b":
+        return G.recipe_groups(model, backbone_lr_scale=0.1, weight_decay=0.01)
+    if setting == "c":
+        return [G.backbone_group(model, frozen=True)]
+    if setting == "d":
+        return [G.feature_extractor_group(model, frozen=True)]
+    raise ValueError(setting)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--settings", default="abcd")
+    ap.add_argument("--steps", type=int, default=150)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--image", type=int, default=224)
+    ap.add_argument("--layers", type=int, default=6)
+    ap.add_argument("--vocab", type=int, default=10000)
+    ap.add_argument("--dropout", type=float, default=0.1)
+    args = ap.parse_args()
+
+    import bench  # synthetic_batch: the benchmark's own batch
+    import fpnmt
+    from fpnmt.layers import Init
+    from fpnmt.train import TrainEngine
+    from models.transformer import Transformer
+    from utils.utils import CustomSchedule
+    fpnmt._lib.assert_in_tree()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_param_groups: needs a GPU (no fallback)")
+    torch.cuda.set_device(0)
+    fpnmt.set_precision("bf16")
+    T_pad = 32
+    img, tok = bench.synthetic_batch(args.batch, args.image, args.vocab, T_pad, 1000, "cuda")
+    engines = {}
+    for s in args.settings:
+        model = Transformer(args.layers, 512, 8, 2048, math.ceil(args.image / 16) ** 2, args.vocab, args.dropout,
+                            max_seq_len=T_pad, backbone="resnet50",
+                            init=Init(torch.Generator().manual_seed(1234))).cuda()
+        eng = TrainEngine(model, CustomSchedule(2048, 4000), use_graph=True, param_groups=groups_for(s, model))
+        for _ in range(max(args.warmup, 3)):
+            eng.step(img, tok)
+        torch.cuda.synchronize()
+        engines[s] = eng
+    times = {s: [] for s in engines}
+    loss = {}
+    for _ in range(args.rounds):
+        for s, eng in engines.items():
+            eng.step(img, tok)  # this engine's graphs and weights back into the caches
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.steps):
+                out = eng.step(img, tok)
+            e1.record()
+            torch.cuda.synchronize()
+            times[s].append(e0.elapsed_time(e1) / args.steps)
+            loss[s] = float(out)
+    res = {"workload": f"C2: ResNet-50 FPN + {args.layers}-layer transformer, {args.image}x{args.image}, batch "
+                       f"{args.batch}, T=31, V={args.vocab}, bf16, dropout {args.dropout}, hipGraph replay",
+           "steps_per_window": args.steps, "rounds": args.rounds, "settings": {}}
+    for s, ts in times.items():
+        med = sorted(ts)[len(ts) // 2]
+        res["settings"][s] = {"ms_per_step": [round(t, 4) for t in ts], "median_ms": round(med, 4),
+                              "spread_ms": round(max(ts) - min(ts), 4), "window_s": round(med * args.steps / 1e3, 3),
+                              "images_per_s": round(args.batch / med * 1e3, 1), "loss": round(loss[s], 5)}
+        a = engines[s].arena
+        sg = engines[s].seg_groups
+        b0, b1 = sg.trim(0, a.nblocks) if sg is not None else (0, a.nblocks)
+        res["settings"][s]["optimizer_blocks_launched"] = [b1 - b0, a.nblocks]
+    if "a" in times:
+        base = res["settings"]["a"]["median_ms"]
+        for s in times:
+            res["settings"][s]["vs_a"] = round(res["settings"][s]["median_ms"] / base, 4)
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()
