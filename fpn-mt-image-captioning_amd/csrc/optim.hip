@@ -195,7 +195,13 @@ __device__ __forceinline__ uint32_t prep_div_c(uint32_t q, const fpnmt_seg_prep&
 // GROUPS: groups[seg] (uniform per block, one 16-B load like preps[seg]) scales
 // the rate, adds decoupled weight decay and marks frozen segments, whose
 // blocks return before any load of the arena, the norms or the prep table.
-template <bool PREP, bool GROUPS>
+// EMA: a shadow copy ema of the parameters follows them as
+// e += omd_t * (p_new - e), one more fp32 stream through the same registers;
+// ema_desc (16 B, device-resident, uniform per block like groups[seg]) holds
+// 1 - decay and the TF debias switch: omd_t = max(1 - decay, 9 / (10 + t)),
+// i.e. decay_t = min(decay, (1 + t) / (10 + t)) written on 1 - decay so that
+// nothing cancels. Frozen segments return before the descriptor is read.
+template <bool PREP, bool GROUPS, bool EMA>
 __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk, const int32_t* __restrict__ blk_seg,
                                               const long long* __restrict__ blk_start, int block_elems,
                                               const long long* __restrict__ off,
@@ -206,7 +212,9 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
                                               const int32_t* __restrict__ seg_blk0,
                                               const long long* __restrict__ step,
                                               const fpnmt_seg_prep* __restrict__ preps,
-                                              const fpnmt_seg_group* __restrict__ groups, float& s_ss,
+                                              const fpnmt_seg_group* __restrict__ groups,
+                                              float* __restrict__ ema,
+                                              const fpnmt_ema_desc* __restrict__ ema_desc, float& s_ss,
                                               unsigned short* s_prep) {
   const int seg = blk_seg[blk];
   float g_scale = 1.f, g_decay = 0.f;
@@ -240,6 +248,12 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
   // tf.clip_by_norm: g * clip / max(||g||, clip)  (||g|| = 0 -> factor 1)
   const float ss = d.clipnorm > 0.f ? (sparse_norm ? sumsq[seg] * d.grad_scale * d.grad_scale : s_ss) : 0.f;
   const float nrm = ss > 0.f ? sqrtf(ss) : 0.f;
+  float omd = 0.f;  // 1 - decay_t of this step
+  if constexpr (EMA) {
+    const fpnmt_ema_desc ed = *ema_desc;
+    omd = ed.debias ? fmaxf(ed.one_minus_decay, 9.f / (10.f + t)) : ed.one_minus_decay;
+  }
+  auto avg = [&](float pi, float& ei) { ei = fmaf(omd, pi - ei, ei); };
   const bool sparse_form = seg_flags && (seg_flags[seg] & 2);
   auto upd = [&](float gr, float& pi, float& mi, float& vi, float& hi) {
     gr *= d.grad_scale;
@@ -260,16 +274,22 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
     }
   };
   // float4 body (block starts are 4-element aligned), U vectors per thread in
-  // flight per array (all 5U loads issued before the first use); streaming
+  // flight per array (all 5U loads, 6U with EMA, issued before the first use); streaming
   // (non-temporal) loads and stores: nothing here is re-read before the next
   // step. Scalar tail for the last < 4 elements of a segment.
-  constexpr int U = 4;
+  // With EMA, U = 2. At U = 4 the sixth stream takes the kernel to 157..175
+  // VGPRs and three of its four instantiations below their twins' occupancy;
+  // at U = 3 (131..149) the plain one still loses a wave. U = 2 (105..123)
+  // runs 4 waves per SIMD everywhere and divides a full block's 16 vectors
+  // per thread evenly (no clamped, repeated loads in a last pass).
+  constexpr int U = EMA ? 2 : 4;
   const long long nv = (b1 - b0) >> 2;
   float4* p4 = reinterpret_cast<float4*>(param + b0);
   const float4* g4 = reinterpret_cast<const float4*>(grad + b0);
   float4* m4 = reinterpret_cast<float4*>(m + b0);
   float4* v4 = reinterpret_cast<float4*>(v + b0);
   float4* h4 = reinterpret_cast<float4*>(vhat + b0);
+  float4* e4 = EMA ? reinterpret_cast<float4*>(ema + b0) : nullptr;
   typedef __attribute__((ext_vector_type(4))) float nf4;
   auto ld = [](const float4* a) {
     const nf4 q = __builtin_nontemporal_load((const nf4*)a);
@@ -322,11 +342,12 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
                            ((uint32_t)__builtin_bit_cast(unsigned short, w3) << 16);
   };
   for (long long i0 = threadIdx.x; i0 < nv; i0 += 256 * U) {
-    float4 G[U], P[U], M[U], V[U], H[U];
+    float4 G[U], P[U], M[U], V[U], H[U], E[EMA ? U : 1];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long long i = min(i0 + 256LL * u, nv - 1);  // clamped: unconditional loads
       G[u] = ld(g4 + i); P[u] = ld(p4 + i); M[u] = ld(m4 + i); V[u] = ld(v4 + i); H[u] = ld(h4 + i);
+      if constexpr (EMA) E[u] = ld(e4 + i);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -337,6 +358,10 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
       upd(G[u].z, P[u].z, M[u].z, V[u].z, H[u].z);
       upd(G[u].w, P[u].w, M[u].w, V[u].w, H[u].w);
       st(m4 + i, M[u]); st(v4 + i, V[u]); st(h4 + i, H[u]); st(p4 + i, P[u]);
+      if constexpr (EMA) {
+        avg(P[u].x, E[u].x); avg(P[u].y, E[u].y); avg(P[u].z, E[u].z); avg(P[u].w, E[u].w);
+        st(e4 + i, E[u]);
+      }
       if constexpr (PREP) {
         if (prep) prep4(i, P[u]);
       }
@@ -377,13 +402,18 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
     v[i] = vi;
     vhat[i] = hi;
     param[i] = pi;
+    if constexpr (EMA) {
+      float ei = ema[i];
+      avg(pi, ei);
+      ema[i] = ei;
+    }
   }
 }
 
 // one workgroup per arena block, or a persistent grid striding over them
 // (gridDim.x < nblocks: the early optimizer part, no compute-copy refresh,
 // sharing the CUs with a running backward)
-template <bool PREP, bool GROUPS>
+template <bool PREP, bool GROUPS, bool EMA>
 __global__ __launch_bounds__(256) void amsgrad_kernel(fpnmt_adam_desc d, int blk_first, int nblocks,
                                                       const int32_t* __restrict__ blk_seg,
                                                       const long long* __restrict__ blk_start, int block_elems,
@@ -396,17 +426,41 @@ __global__ __launch_bounds__(256) void amsgrad_kernel(fpnmt_adam_desc d, int blk
                                                       const int32_t* __restrict__ seg_blk0,
                                                       const long long* __restrict__ step,
                                                       const fpnmt_seg_prep* __restrict__ preps,
-                                                      const fpnmt_seg_group* __restrict__ groups) {
+                                                      const fpnmt_seg_group* __restrict__ groups,
+                                                      float* __restrict__ ema,
+                                                      const fpnmt_ema_desc* __restrict__ ema_desc) {
   __shared__ float s_ss;
   __shared__ unsigned short s_prep[PREP ? PREP_LDS : 1];
   for (int b = (int)blockIdx.x; b < nblocks; b += (int)gridDim.x) {
     if (b != (int)blockIdx.x) __syncthreads();  // the previous block's LDS reads are done
-    amsgrad_block<PREP, GROUPS>(d, blk_first + b, blk_seg, blk_start, block_elems, off, seg_flags, param, grad, m, v,
-                                vhat, sumsq, blk_part, seg_blk0, step, preps, groups, s_ss, s_prep);
+    amsgrad_block<PREP, GROUPS, EMA>(d, blk_first + b, blk_seg, blk_start, block_elems, off, seg_flags, param, grad,
+                                     m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, groups, ema, ema_desc, s_ss,
+                                     s_prep);
   }
 }
 
 __global__ void step_inc_kernel(long long* step) { *step += 1; }
+
+// a <-> b in place: float4 body when both pointers are 16-B aligned (the
+// arenas are), scalar otherwise and for the last < 4 elements; grid-stride
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, long long n,
+                                                       int vec) {
+  const long long tid = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  const long long nth = (long long)gridDim.x * blockDim.x;
+  const long long nv = vec ? n >> 2 : 0;
+  float4* a4 = reinterpret_cast<float4*>(a);
+  float4* b4 = reinterpret_cast<float4*>(b);
+  for (long long i = tid; i < nv; i += nth) {
+    const float4 x = a4[i], y = b4[i];
+    a4[i] = y;
+    b4[i] = x;
+  }
+  for (long long i = (nv << 2) + tid; i < n; i += nth) {
+    const float x = a[i], y = b[i];
+    a[i] = y;
+    b[i] = x;
+  }
+}
 
 }  // namespace fpnmt
 
@@ -502,7 +556,8 @@ static int amsgrad_launch(const fpnmt_adam_desc* d, int blk_first, int nblocks, 
                           const long long* off, const int32_t* seg_flags, float* param, const float* grad,
                           float* m, float* v, float* vhat, const float* sumsq, const float* blk_part,
                           const int32_t* seg_blk0, long long* step, const fpnmt_seg_prep* preps,
-                          const fpnmt_seg_group* groups, fpnmt_stream_t stream) {
+                          const fpnmt_seg_group* groups, float* ema, const fpnmt_ema_desc* ema_desc,
+                          fpnmt_stream_t stream) {
   if (!d || !step) return fail(FPNMT_E_ARG, "amsgrad: null");
   if (blk_first < 0 || max_grid < 0) return fail(FPNMT_E_ARG, "amsgrad: negative first block / grid");
   const int grid = max_grid > 0 ? std::min(nblocks, max_grid) : nblocks;
@@ -511,16 +566,20 @@ static int amsgrad_launch(const fpnmt_adam_desc* d, int blk_first, int nblocks, 
   if (preps && (!seg_blk0 || block_elems > 16384 || block_elems % 4096))
     return fail(FPNMT_E_ARG, "amsgrad_prep: needs seg_blk0 and block_elems a multiple of 4096 (<= 16384)");
   if (nblocks > 0) {
-#define FPNMT_AMSGRAD_LAUNCH(PREP, GROUPS)                                                                       \
-  hipLaunchKernelGGL((amsgrad_kernel<PREP, GROUPS>), dim3(grid), dim3(256), 0, S(stream), *d, blk_first, nblocks, \
-                     blk_seg, blk_start, block_elems, off, seg_flags, param, grad, m, v, vhat, sumsq, blk_part,   \
-                     seg_blk0, step, PREP ? preps : (const fpnmt_seg_prep*)nullptr,                               \
-                     GROUPS ? groups : (const fpnmt_seg_group*)nullptr)
-    if (groups) {
-      if (preps) FPNMT_AMSGRAD_LAUNCH(true, true); else FPNMT_AMSGRAD_LAUNCH(false, true);
-    } else {
-      if (preps) FPNMT_AMSGRAD_LAUNCH(true, false); else FPNMT_AMSGRAD_LAUNCH(false, false);
-    }
+#define FPNMT_AMSGRAD_LAUNCH(PREP, GROUPS, EMA)                                                                   \
+  hipLaunchKernelGGL((amsgrad_kernel<PREP, GROUPS, EMA>), dim3(grid), dim3(256), 0, S(stream), *d, blk_first,      \
+                     nblocks, blk_seg, blk_start, block_elems, off, seg_flags, param, grad, m, v, vhat, sumsq,     \
+                     blk_part, seg_blk0, step, PREP ? preps : (const fpnmt_seg_prep*)nullptr,                      \
+                     GROUPS ? groups : (const fpnmt_seg_group*)nullptr, EMA ? ema : (float*)nullptr,               \
+                     EMA ? ema_desc : (const fpnmt_ema_desc*)nullptr)
+#define FPNMT_AMSGRAD_PICK(EMA)                                                                     \
+  if (groups) {                                                                                     \
+    if (preps) FPNMT_AMSGRAD_LAUNCH(true, true, EMA); else FPNMT_AMSGRAD_LAUNCH(false, true, EMA);   \
+  } else {                                                                                          \
+    if (preps) FPNMT_AMSGRAD_LAUNCH(true, false, EMA); else FPNMT_AMSGRAD_LAUNCH(false, false, EMA); \
+  }
+    if (ema) { FPNMT_AMSGRAD_PICK(true) } else { FPNMT_AMSGRAD_PICK(false) }
+#undef FPNMT_AMSGRAD_PICK
 #undef FPNMT_AMSGRAD_LAUNCH
   }
   if (inc_step) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, S(stream), step);
@@ -534,7 +593,8 @@ int fpnmt_amsgrad_step_part(const fpnmt_adam_desc* d, int blk_first, int nblocks
                             const int32_t* seg_blk0, long long* step, const fpnmt_seg_prep* preps,
                             fpnmt_stream_t stream) {
   return amsgrad_launch(d, blk_first, nblocks, inc_step, max_grid, blk_seg, blk_start, block_elems, off, seg_flags,
-                        param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, nullptr, stream);
+                        param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, nullptr, nullptr, nullptr,
+                        stream);
 }
 
 int fpnmt_amsgrad_step_groups(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
@@ -545,7 +605,35 @@ int fpnmt_amsgrad_step_groups(const fpnmt_adam_desc* d, int blk_first, int nbloc
                               const fpnmt_seg_group* groups, fpnmt_stream_t stream) {
   if (!groups) return fail(FPNMT_E_ARG, "amsgrad_step_groups: null group table");
   return amsgrad_launch(d, blk_first, nblocks, inc_step, max_grid, blk_seg, blk_start, block_elems, off, seg_flags,
-                        param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, groups, stream);
+                        param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, groups, nullptr, nullptr,
+                        stream);
+}
+
+int fpnmt_amsgrad_step_ema(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
+                           const int32_t* blk_seg, const long long* blk_start, int block_elems,
+                           const long long* off, const int32_t* seg_flags, float* param, const float* grad,
+                           float* m, float* v, float* vhat, const float* sumsq, const float* blk_part,
+                           const int32_t* seg_blk0, long long* step, const fpnmt_seg_prep* preps,
+                           const fpnmt_seg_group* groups, float* ema, const fpnmt_ema_desc* ema_desc,
+                           fpnmt_stream_t stream) {
+  if (!ema || !ema_desc) return fail(FPNMT_E_ARG, "amsgrad_step_ema: null ema / descriptor");
+  if (ema == param || ema == m || ema == v || ema == vhat || ema == grad)
+    return fail(FPNMT_E_ARG, "amsgrad_step_ema: ema aliases another array");
+  return amsgrad_launch(d, blk_first, nblocks, inc_step, max_grid, blk_seg, blk_start, block_elems, off, seg_flags,
+                        param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, groups, ema, ema_desc,
+                        stream);
+}
+
+int fpnmt_swap_f32(float* a, float* b, long long n, fpnmt_stream_t stream) {
+  if (n < 0) return fail(FPNMT_E_ARG, "swap_f32: n < 0");
+  if (n == 0) return 0;
+  if (!a || !b) return fail(FPNMT_E_ARG, "swap_f32: null");
+  if (a < b ? a + n > b : b + n > a) return fail(FPNMT_E_ARG, "swap_f32: the buffers overlap");
+  const int vec = (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
+  const long long work = vec ? (n + 3) >> 2 : n;
+  const int grid = (int)std::min<long long>(4096, (work + 255) / 256);
+  hipLaunchKernelGGL(swap_f32_kernel, dim3(grid), dim3(256), 0, S(stream), a, b, n, vec);
+  return check_launch("swap_f32");
 }
 
 int fpnmt_amsgrad_step_prep(const fpnmt_adam_desc* d, int nblocks, const int32_t* blk_seg,

@@ -141,6 +141,10 @@ class SegGroup(C.Structure):
     _fields_ = [("lr_scale", C.c_float), ("weight_decay", C.c_float), ("frozen", C.c_int32), ("reserved", C.c_int32)]
 
 
+class EmaDesc(C.Structure):
+    _fields_ = [("one_minus_decay", C.c_float), ("debias", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 P = C.c_void_p
 I = C.c_int
 LL = C.c_longlong
@@ -223,6 +227,9 @@ SIGNATURES = {
     "fpnmt_grad_sumsq_groups": [I, I, I, P, P, I, P, P, P, P, F, P, P],
     "fpnmt_amsgrad_step_groups": [C.POINTER(AdamDesc), I, I, I, I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P,
                                   P],
+    "fpnmt_amsgrad_step_ema": [C.POINTER(AdamDesc), I, I, I, I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                               P],
+    "fpnmt_swap_f32": [P, P, LL, P],
     "fpnmt_decode_attention": [I, I, I, I, I, F, P, LL, P, LL, LL, LL, LL, P, I, I, P, LL, P],
     "fpnmt_beam_step": [I, I, I, P, LL, P, P, P, I, I, P, P, I, I, P, P, I, P, P, P],
     "fpnmt_beam_step_log": [I, I, I, P, LL, P, P, P, P, P, I, I, P, P, I, I, P, P, P],

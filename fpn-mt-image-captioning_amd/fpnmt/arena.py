@@ -82,6 +82,57 @@ class SegGroups:
         return b0, b1
 
 
+def check_ema_decay(decay, who="ema_decay"):
+    """decay as a float in [0, 1); anything else, NaN included, is refused."""
+    try:
+        d = float(decay)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who} must lie in [0, 1), got {decay!r}") from None
+    if not 0.0 <= d < 1.0:  # NaN fails both comparisons
+        raise ValueError(f"{who} must lie in [0, 1), got {decay!r}")
+    return d
+
+
+def ema_one_minus_decay(decay):
+    """The fp32 value the kernel gets: 1 - decay in double, rounded once."""
+    import struct
+    return struct.unpack("f", struct.pack("f", 1.0 - check_ema_decay(decay)))[0]
+
+
+def ema_omd_t(one_minus_decay, debias, t):
+    """Host restatement (double) of the kernel's 1 - decay_t at t = iterations
+    + 1: TF's min(decay, (1 + t) / (10 + t)) written on 1 - decay."""
+    return max(one_minus_decay, 9.0 / (10.0 + t)) if debias else one_minus_decay
+
+
+class EmaDesc:
+    """The 16-byte fpnmt_ema_desc of an arena on its device and its host
+    mirror (decay, one_minus_decay, debias). Like SegGroups' table it is
+    allocated once and only ever written in place (stream-ordered): captured
+    optimizer graphs hold its pointer and read the values of the moment they
+    replay."""
+
+    def __init__(self, device, decay, debias=True):
+        self.table = torch.zeros(4, dtype=torch.int32, device=device)
+        self._f32 = self.table.view(torch.float32)
+        self.set(decay, debias)
+
+    def set(self, decay, debias=None):
+        self.decay = check_ema_decay(decay)
+        self.one_minus_decay = ema_one_minus_decay(self.decay)
+        if debias is not None:
+            self.debias = bool(debias)
+        d = L.EmaDesc()
+        d.one_minus_decay, d.debias = self.one_minus_decay, int(self.debias)
+        host = torch.frombuffer(bytearray(bytes(d)), dtype=torch.int32)
+        self.table.copy_(host)  # in place: the pointer captured graphs hold stays
+
+    def host(self):
+        """The descriptor as the device holds it (one_minus_decay, debias)."""
+        t = self.table.cpu()
+        return float(t.view(torch.float32)[0]), int(t[1])
+
+
 class ParamArena:
     def __init__(self, params, device, sparse_names=()):
         """params: ordered list of (name, nn.Parameter) — shared parameters
@@ -156,6 +207,46 @@ class ParamArena:
         self.seg_bounds = self.seg_bounds.to(dev)
         self.seg_flags = torch.tensor(flags or [0], dtype=torch.int32, device=dev)
         self.preparers = []
+        self.ema = None  # enable_ema(): the averaged parameters, this arena's layout
+        self.ema_desc = None
+
+    # ---------------------------------------------------- weight averaging
+    def enable_ema(self, decay, debias=True):
+        """Allocate the shadow arena `ema` (fp32, the layout of `flat`) and
+        its device descriptor. ema starts as a copy of flat, as
+        tf.train.ExponentialMovingAverage initialises a shadow variable;
+        amsgrad_step(..., ema=True) then keeps
+        e += (1 - decay_t) * (p_new - e) inside the optimizer kernel, with
+        decay_t = min(decay, (1 + t) / (10 + t)) when debias is set."""
+        desc = EmaDesc(self.device, decay, debias)  # refuses a bad decay before anything is allocated
+        if self.ema is None:
+            self.ema = self.flat.detach().clone()
+            self.ema_desc = desc
+        else:  # already enabled: new values in place, the average is kept
+            self.ema_desc.set(decay, debias)
+        return self.ema
+
+    def set_ema_decay(self, decay):
+        """A new decay from the next step on, written into the device
+        descriptor in place (stream-ordered; no recapture)."""
+        if self.ema_desc is None:
+            raise ValueError("ParamArena: enable_ema() first")
+        self.ema_desc.set(decay)
+
+    def reset_ema(self):
+        """ema = flat (a new phase of a recipe starts its average afresh)."""
+        if self.ema is None:
+            raise ValueError("ParamArena: enable_ema() first")
+        with torch.no_grad():
+            self.ema.copy_(self.flat)
+
+    def swap_ema(self):
+        """flat <-> ema in place (fpnmt_swap_f32): the parameters, which are
+        views of flat, then read the averaged values; a second call puts
+        both back bit for bit."""
+        if self.ema is None:
+            raise ValueError("ParamArena: enable_ema() first")
+        L.call("fpnmt_swap_f32", L.ptr(self.flat), L.ptr(self.ema), self.total, L.stream_ptr())
 
     # -------------------------------------------------------------- grads
     def zero_grad(self, max_blocks=0):
@@ -193,7 +284,7 @@ class ParamArena:
         return self._seg_blk0_host[i]
 
     def amsgrad_step(self, lr_schedule, beta1=0.9, beta2=0.98, eps=1e-9, clipnorm=1.0, grad_scale=1.0,
-                     preps=None, blocks=None, inc_step=True, max_grid=0, groups=None):
+                     preps=None, blocks=None, inc_step=True, max_grid=0, groups=None, ema=False):
         """Keras AMSGrad + per-tensor clip_by_norm over the arena. preps: a
         device table of fpnmt_seg_prep (one per segment, layers.FusedPrep)
         whose non-null entries get their bf16 compute copies written by the
@@ -204,7 +295,11 @@ class ParamArena:
         this arena (make_groups): the step through fpnmt_amsgrad_step_groups
         with its per-segment rate scale, decoupled weight decay and frozen
         flags; frozen segments at either end of the range are not launched.
-        None: the plain entry points, as before."""
+        None: the plain entry points, as before. ema: the step through
+        fpnmt_amsgrad_step_ema (with or without groups), which also advances
+        the shadow arena of enable_ema(); False: the entry points above."""
+        if ema and self.ema is None:
+            raise ValueError("ParamArena.amsgrad_step(ema=True): enable_ema() first")
         d = L.AdamDesc()
         d.beta1, d.beta2, d.eps, d.clipnorm = beta1, beta2, eps, clipnorm
         d.grad_scale = grad_scale
@@ -218,6 +313,26 @@ class ParamArena:
             d.sched_warm_pow = float(lr_schedule.warmup_steps ** -1.5)
         b0, b1 = (0, self.nblocks) if blocks is None else blocks
         s = L.stream_ptr()
+        if ema:
+            gt = None
+            if groups is not None:
+                b0, b1 = groups.trim(b0, b1)
+                gt = L.ptr(groups.table)
+            if clipnorm > 0 and b1 > b0:
+                if gt is not None:
+                    L.call("fpnmt_grad_sumsq_groups", b0, b1 - b0, max_grid, L.ptr(self.blk_seg),
+                           L.ptr(self.blk_start), BLOCK_ELEMS, L.ptr(self.seg_bounds), L.ptr(self.seg_flags), gt,
+                           L.ptr(self.grad), grad_scale, L.ptr(self.blk_part), s)
+                else:
+                    L.call("fpnmt_grad_sumsq_part", b0, b1 - b0, max_grid, L.ptr(self.blk_seg),
+                           L.ptr(self.blk_start), BLOCK_ELEMS, L.ptr(self.seg_bounds), L.ptr(self.seg_flags),
+                           L.ptr(self.grad), grad_scale, L.ptr(self.blk_part), s)
+            L.call("fpnmt_amsgrad_step_ema", d, b0, b1 - b0, 1 if inc_step else 0, max_grid, L.ptr(self.blk_seg),
+                   L.ptr(self.blk_start), BLOCK_ELEMS, L.ptr(self.seg_bounds), L.ptr(self.seg_flags),
+                   L.ptr(self.flat), L.ptr(self.grad), L.ptr(self.m), L.ptr(self.v), L.ptr(self.vhat),
+                   L.ptr(self.sumsq), L.ptr(self.blk_part), L.ptr(self.seg_blk0), L.ptr(self.step),
+                   L.ptr(preps) if preps is not None else None, gt, L.ptr(self.ema), L.ptr(self.ema_desc.table), s)
+            return
         if groups is not None:
             b0, b1 = groups.trim(b0, b1)
             gt = L.ptr(groups.table)

@@ -8,9 +8,16 @@ checkpoint holding
   model/<state_dict key>           every parameter and buffer (fp32 masters,
                                    Keras layouts, frozen-BN statistics)
   optimizer/{m,v,vhat}/<param>     the AMSGrad slots of every trainable tensor
+  optimizer/ema/<param>            the averaged parameters, when the engine
+                                   keeps an average (TrainEngine(ema_decay=...))
   optimizer/iterations             Keras `iterations` (int64, drives the lr
                                    schedule and the bias correction)
 keyed by parameter NAME, so a checkpoint restores into any arena ordering.
+The ema keys are optional under the same format tag: a checkpoint without
+them restored into an averaging engine starts the average at the restored
+parameters, and an engine without an average ignores them.
+Checkpoint.export_ema(path) writes a model-only file whose model/ tensors are
+the averaged ones, which any Pipeline loads for inference.
 A small JSON index (`checkpoint`) in the directory lists the files, newest
 last, like TF's `checkpoint` state file.
 
@@ -55,7 +62,8 @@ class Checkpoint:
             a = eng.arena
             for name, p, off in zip(a.names, a.params, a.offsets):
                 n = p.numel()
-                for slot, buf in (("m", a.m), ("v", a.v), ("vhat", a.vhat)):
+                slots = (("m", a.m), ("v", a.v), ("vhat", a.vhat)) + ((("ema", a.ema),) if a.ema is not None else ())
+                for slot, buf in slots:
                     out[f"optimizer/{slot}/{name}"] = buf[off:off + n].view(p.shape).detach().cpu().clone()
             out["optimizer/iterations"] = a.step.detach().cpu().clone()
         return out
@@ -67,6 +75,36 @@ class Checkpoint:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             tmp = path + ".tmp"
             save_file(self.state_tensors(), tmp, metadata={"format": FORMAT, "save_counter": str(self.save_counter)})
+            os.replace(tmp, path)
+        if dist.is_initialized():
+            dist.barrier()
+        return path
+
+    def export_ema(self, path):
+        """A model-only checkpoint (no optimizer/ keys) whose model/<param>
+        tensors are the engine's averaged parameters; buffers, which are not
+        averaged, are the model's current ones. Restores into any model of
+        the same architecture (Checkpoint(transformer).restore, a Pipeline's
+        checkpoint directory) for inference."""
+        from safetensors.torch import save_file
+        eng = self.optimizer
+        if eng is None or eng.arena.ema is None:
+            raise ValueError("export_ema: the checkpoint's optimizer keeps no average (TrainEngine(ema_decay=...))")
+        if getattr(eng, "_ema_open", False):
+            raise RuntimeError("export_ema inside ema_weights(): the arenas are swapped")
+        a = eng.arena
+        name_of = {id(p): n for n, p in self.transformer.named_parameters()}
+        avg = {}
+        for p, off in zip(a.params, a.offsets):
+            avg["model/" + name_of[id(p)]] = a.ema[off:off + p.numel()].view(p.shape).detach().cpu().clone()
+        out = {}
+        for k, v in self.transformer.state_dict().items():
+            t = avg.get("model/" + k)
+            out["model/" + k] = t if t is not None else v.detach().to("cpu", copy=True).contiguous()
+        if _is_writer():
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            tmp = path + ".tmp"
+            save_file(out, tmp, metadata={"format": FORMAT, "save_counter": str(self.save_counter), "weights": "ema"})
             os.replace(tmp, path)
         if dist.is_initialized():
             dist.barrier()
@@ -100,6 +138,18 @@ class Checkpoint:
                     for slot, buf in (("m", a.m), ("v", a.v), ("vhat", a.vhat)):
                         buf[off:off + n].copy_(f.get_tensor(f"optimizer/{slot}/{name}").reshape(-1))
                 a.step.copy_(f.get_tensor("optimizer/iterations"))
+            if eng is not None and eng.arena.ema is not None:
+                # after the model tensors: without ema keys (a checkpoint of an
+                # engine without an average, or a model-only one) the average
+                # starts at the restored parameters
+                a = eng.arena
+                if getattr(eng, "_ema_open", False):
+                    raise RuntimeError("restore inside ema_weights(): the arenas are swapped")
+                a.ema.copy_(a.flat)
+                for name, p, off in zip(a.names, a.params, a.offsets):
+                    key = f"optimizer/ema/{name}"
+                    if key in keys:
+                        a.ema[off:off + p.numel()].copy_(f.get_tensor(key).reshape(-1))
             self.save_counter = int(meta.get("save_counter", self.save_counter))
         for m in self.transformer.modules():  # frozen-BN folds read the restored statistics
             if hasattr(m, "refresh_bn") and getattr(m, "bn_scale", None) is not None:

@@ -43,6 +43,8 @@ all of them (stream waits; the host never blocks).
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.distributed as dist
 
@@ -51,7 +53,7 @@ from . import _lib as L
 from . import dist as fdist
 from . import layers as flayers
 from . import ops
-from .arena import ParamArena
+from .arena import ParamArena, check_ema_decay
 from .layers import group_param_order
 from . import param_groups as pgroups
 
@@ -59,7 +61,7 @@ from . import param_groups as pgroups
 class TrainEngine:
     def __init__(self, transformer, schedule, beta1=0.9, beta2=0.98, eps=1e-9, clipnorm=1.0, use_graph=True,
                  group=None, bucket_bytes=fdist.DEFAULT_BUCKET_BYTES, split_backward=None, bucket_dtype=None,
-                 sync_bn=True, label_smoothing=0.0, param_groups=None):
+                 sync_bn=True, label_smoothing=0.0, param_groups=None, ema_decay=None, ema_debias=True):
         """param_groups: None runs the plain step (every trainable tensor at
         the schedule's rate, no decay: the reference's optimizer). A list of
         fpnmt.param_groups.ParamGroup (an empty one included) runs the same
@@ -67,12 +69,28 @@ class TrainEngine:
         decoupled weight decay and frozen flags. Every tensor that is
         trainable at construction stays in the arena, frozen ones included:
         optimizer state and checkpoints keep one layout across phases, and
-        set_lr_scale / set_weight_decay / set_frozen change a group later."""
+        set_lr_scale / set_weight_decay / set_frozen change a group later.
+
+        ema_decay: None (the default) keeps no average and runs the entry
+        points above. A number in [0, 1) keeps an exponential moving average
+        of every trainable parameter in a shadow arena (arena.ema, fp32),
+        updated inside the optimizer kernel (fpnmt_amsgrad_step_ema) as
+        tf.train.ExponentialMovingAverage would after each step:
+        e += (1 - decay_t) * (p - e), with decay_t = min(ema_decay,
+        (1 + t) / (10 + t)) when ema_debias is set (TF's num_updates form,
+        t = the step count) and ema_decay otherwise. Parameters, optimizer
+        state and losses are bit for bit those of the engine without it.
+        ema_weights() puts the average under the model; set_ema_decay /
+        reset_ema change it between steps. Under data parallelism every rank
+        keeps its own average: the parameters are bitwise equal across ranks
+        after every step, so the averages are too, and nothing is exchanged."""
         from models.transformer import create_masks  # noqa: F401 (ensures import path)
         groups_in = pgroups.validate(param_groups) if param_groups is not None else None
         if not 0.0 <= float(label_smoothing) < 1.0:  # NaN fails both comparisons
             raise ValueError(f"TrainEngine: label_smoothing must lie in [0, 1), got {label_smoothing!r}")
         self.label_smoothing = float(label_smoothing)
+        if ema_decay is not None:
+            ema_decay = check_ema_decay(ema_decay, "TrainEngine: ema_decay")
         self.model = transformer
         self.schedule = schedule
         self.adam = dict(beta1=beta1, beta2=beta2, eps=eps, clipnorm=clipnorm)
@@ -155,6 +173,11 @@ class TrainEngine:
                 # collectives on one communicator
                 self.bn_group = fdist.new_group_like(group)
                 fdist.set_sync_batchnorm(transformer, self.bn_group)
+        # weight averaging: the shadow arena starts as a copy of the (broadcast)
+        # parameters; its descriptor is allocated once, captured graphs hold it
+        self._ema_open = False
+        if ema_decay is not None:
+            self.arena.enable_ema(ema_decay, ema_debias)
         flayers.invalidate_weights()
         self.dtype = None
         self.use_graph = use_graph
@@ -284,6 +307,72 @@ class TrainEngine:
         self._wsteps = {}
         flayers.invalidate_weights()  # an unfrozen layer comes back into the refresh
 
+    # ----------------------------------------------------- weight averaging
+    def _require_ema(self, who):
+        if self.arena.ema is None:
+            raise ValueError(f"TrainEngine.{who}: the engine was built without ema_decay")
+
+    @property
+    def ema_decay(self):
+        """The decay in force (None: no average is kept)."""
+        return self.arena.ema_desc.decay if self.arena.ema_desc is not None else None
+
+    def set_ema_decay(self, decay):
+        """A new decay in [0, 1) from the next step on. Written into the
+        device descriptor in place (stream-ordered): the captured graphs are
+        kept and the next replay reads the new value, like set_lr_scale."""
+        self._require_ema("set_ema_decay")
+        self.arena.set_ema_decay(check_ema_decay(decay, "TrainEngine.set_ema_decay"))
+
+    def reset_ema(self):
+        """The average restarts from the current parameters (a new phase of a
+        recipe). The step counter, and with it the debias term, goes on."""
+        self._require_ema("reset_ema")
+        if self._ema_open:
+            raise RuntimeError("TrainEngine.reset_ema inside ema_weights(): the arenas are swapped")
+        self.arena.reset_ema()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate, decode or save on the averaged weights:
+
+            with engine.ema_weights():
+                engine.eval_step(img, tok)
+
+        On entry the parameter arena and the average are exchanged in place
+        (fpnmt_swap_f32: every nn.Parameter stays the view it was, so captured
+        eval and decode graphs go on reading the same addresses) and the
+        compute copies are rebuilt from the averaged masters; on exit both are
+        put back. The exchange is exact, so the training state afterwards is
+        bit for bit what it was. step / step_weighted raise while it is open.
+
+        Only parameters are averaged. Buffers are not: BatchNorm moving
+        statistics (MobileNetV2) and the frozen-BN folds of the ResNet
+        backbone are the model's current ones inside the context too."""
+        self._require_ema("ema_weights")
+        if self._ema_open:
+            raise RuntimeError("TrainEngine.ema_weights: already open")
+        self._swap_ema()
+        self._ema_open = True
+        try:
+            yield self
+        finally:
+            self._ema_open = False
+            self._swap_ema()
+
+    def _swap_ema(self):
+        self.arena.swap_ema()
+        flayers.invalidate_weights()
+        # every copy in use is rewritten in the buffer it lives in: graphs that
+        # eval_step or a decoder captured read the new values at their next
+        # replay, and eval_step has nothing left to refresh
+        flayers.prepare_all(self.model, fpnmt.compute_dtype())
+        self._eval_gen = flayers._GEN[0]
+
+    def _check_trainable_now(self, who):
+        if self._ema_open:
+            raise RuntimeError(f"TrainEngine.{who} inside ema_weights(): the model holds the averaged weights")
+
     # ------------------------------------------------------------ pieces
     def _one(self, loss):
         """The loss's seed gradient, kept across steps (loss.backward() would
@@ -370,7 +459,8 @@ class TrainEngine:
             # every CU slot until it drained (profiles/r05/early_update_r5h.txt)
             self.arena.amsgrad_step(self.schedule, grad_scale=1.0 / self.world, preps=None,
                                     blocks=(0, self.early_blocks), inc_step=False,
-                                    max_grid=fpnmt.config.early_update_grid, groups=self.seg_groups, **self.adam)
+                                    max_grid=fpnmt.config.early_update_grid, groups=self.seg_groups,
+                                    ema=self.arena.ema is not None, **self.adam)
         self._early_pending = True
 
     def _fwd_bwd_split(self, img, tok, weights=None):
@@ -463,7 +553,7 @@ class TrainEngine:
                 skip = {id(m) for m in fp._mods
                         if self.arena.offsets[self.arena.index[id(m.kernel)]] >= self.split_at}
         self.arena.amsgrad_step(self.schedule, grad_scale=1.0 / self.world, preps=fp.table if fp else None,
-                                blocks=blocks, groups=self.seg_groups, **self.adam)
+                                blocks=blocks, groups=self.seg_groups, ema=self.arena.ema is not None, **self.adam)
         if self._frozen_layers:
             # frozen masters do not change: their (fresh) copies need no refresh
             skip = set(skip) | {i for i, m in self._frozen_layers.items() if m._gen == flayers._GEN[0]}
@@ -509,6 +599,7 @@ class TrainEngine:
     # -------------------------------------------------------------- step
     def step(self, img, tok):
         """One training step; returns the (device) loss of this batch."""
+        self._check_trainable_now("step")
         self.calls += 1
         if not self.use_graph or self.calls == 1:
             import fpnmt
@@ -546,6 +637,7 @@ class TrainEngine:
         if tuple(weights.shape) != (tok.shape[0],) or weights.dtype != torch.float32:
             raise ValueError(f"step_weighted: weights must be fp32 of shape ({tok.shape[0]},), "
                              f"got {weights.dtype} {tuple(weights.shape)}")
+        self._check_trainable_now("step_weighted")
         key = (tuple(img.shape), tuple(tok.shape), tok.dtype)
         ent = self._wsteps.setdefault(key, [0, None, None])
         ent[0] += 1

@@ -57,7 +57,7 @@ class Pipeline:
                  image_size=IMAGE_INPUT_SIZE, n_layers=num_layers, backbone=None, rate=DROPOUT_RATE,
                  device="cuda", init=None, use_graph=True, clipnorm_mode=CLIPNORM_MODE, max_to_keep=100,
                  data_dir=DATADIR, data_type_val=DATATYPE_VAL, label_smoothing=0.0, param_groups=None,
-                 backbone_lr_scale=1.0, freeze=(), weight_decay=0.0):
+                 backbone_lr_scale=1.0, freeze=(), weight_decay=0.0, ema_decay=None, ema_debias=True):
         """param_groups (a list of fpnmt.param_groups.ParamGroup), or the
         common cases by keyword: backbone_lr_scale (the CNN backbone at that
         fraction of the transformer's rate), freeze (a subset of {"backbone",
@@ -65,7 +65,14 @@ class Pipeline:
         The keywords build the groups "backbone", "feature_extractor" (the
         FPN and heads) and "transformer", whose values
         engine.set_lr_scale / set_weight_decay / set_frozen change later. Not
-        in the reference; at the defaults the step is the reference's."""
+        in the reference; at the defaults the step is the reference's.
+
+        ema_decay in [0, 1) keeps an exponential moving average of the
+        parameters inside the optimizer step (TrainEngine(ema_decay=...),
+        ema_debias as in tf.train.ExponentialMovingAverage(num_updates=...));
+        eval_step, validate, score_captions, predict_batch and evaluate then
+        take weights="ema" to run on the averaged weights, and checkpoints
+        carry the average. None (the default): no average, the step as before."""
         self.max_seq_len = max_seq_len
         self._metric_eval_src = (data_dir, data_type_val)
         self._metric_eval = None
@@ -89,7 +96,8 @@ class Pipeline:
         self.engine = TrainEngine(self.transformer, self.learning_rate, beta1=0.9, beta2=0.98, eps=1e-9,
                                   clipnorm=clipnorm_for(clipnorm_mode), use_graph=use_graph,
                                   label_smoothing=label_smoothing,  # not in the reference; 0: its one-hot loss
-                                  param_groups=param_groups if param_groups is not None else recipe)
+                                  param_groups=param_groups if param_groups is not None else recipe,
+                                  ema_decay=ema_decay, ema_debias=ema_debias)
         self.optimizer = self.engine
         self.train_loss = Mean(name="train_loss")  # pipeline.py:35
         self.checkpoint_path = checkpoint_path
@@ -114,6 +122,20 @@ class Pipeline:
             from dataset import MetricEval
             self._metric_eval = MetricEval(*self._metric_eval_src)
         return self._metric_eval
+
+    def _weights(self, weights):
+        """The context a call runs in: weights="model" the trained parameters
+        (nothing to do), "ema" the averaged ones (engine.ema_weights(): the
+        arenas exchanged and the compute copies rebuilt, both put back at the
+        end; buffers such as BatchNorm statistics are not averaged)."""
+        import contextlib
+        if weights == "model":
+            return contextlib.nullcontext()
+        if weights != "ema":
+            raise ValueError(f"weights must be 'model' or 'ema', got {weights!r}")
+        if self.engine.arena.ema is None:
+            raise ValueError("weights='ema' needs a Pipeline built with ema_decay")
+        return self.engine.ema_weights()
 
     def loss(self, real, pred):
         """Masked sparse CE from logits, mean over ALL positions (pipeline.py:50-57)."""
@@ -173,15 +195,17 @@ class Pipeline:
                        top_k=top_k, top_p=top_p, seed=seed, image_keys=image_keys)
 
     # ----------------------------------------------------------- held out
-    def eval_step(self, img, caption_token):
+    def eval_step(self, img, caption_token, weights="model"):
         """The loss of one held-out batch without an optimizer step (not in the
         reference): the model in inference mode, nothing written. Returns the
         device tensors of TrainEngine.eval_step: "loss" (comparable with
         train_loss at the same label_smoothing), per caption "caption_logp",
-        "caption_len", "caption_hit", and "totals" (3,) f64."""
-        return self.engine.eval_step(img, caption_token)
+        "caption_len", "caption_hit", and "totals" (3,) f64. weights="ema":
+        on the averaged weights (Pipeline(ema_decay=...))."""
+        with self._weights(weights):
+            return self.engine.eval_step(img, caption_token)
 
-    def validate(self, batches):
+    def validate(self, batches, weights="model"):
         """Held-out loss over an iterable of (img, caption_token) batches, of
         any shapes (a short last batch runs eagerly, as in train_step). The
         sums of log-probability, tokens and arg-max hits accumulate on the
@@ -189,19 +213,21 @@ class Pipeline:
         dict: "token_nll", "perplexity" = exp(token_nll), "token_accuracy",
         "tokens", "captions", "totals". Under data parallelism every rank
         validates its shard; the totals are plain sums and add. An empty
-        iterable raises ValueError."""
+        iterable raises ValueError. weights="ema": on the averaged weights,
+        exchanged once around the whole loop."""
         from fpnmt.evalstats import summarize
         eng = self.engine
         eng.reset_eval_totals()
         captions = 0
-        for img, tok in batches:
-            eng.eval_step(img, tok, accumulate=True)
-            captions += int(tok.shape[0])
+        with self._weights(weights):
+            for img, tok in batches:
+                eng.eval_step(img, tok, accumulate=True)
+                captions += int(tok.shape[0])
         if captions == 0:
             raise ValueError("validate: no batches")
         return summarize(eng.eval_totals.cpu().tolist(), captions)
 
-    def score_captions(self, images, captions, n_per_image=1):
+    def score_captions(self, images, captions, n_per_image=1, weights="model"):
         """Teacher-forced log-probabilities of given captions: images
         (B, H, W, 3) on the GPU, captions B * n_per_image token-id lists
         without <start> / <end>, image-major. Returns per caption
@@ -209,7 +235,7 @@ class Pipeline:
         convention of predict_batch's mode="beam" (length_alpha 0) and
         mode="sample", so n-best lists and external captions can be reranked
         with it. A caption of more than max_seq_len - 1 tokens raises
-        ValueError."""
+        ValueError. weights="ema": scored by the averaged weights."""
         from fpnmt.scst import pack_tokens
         caps = [[int(t) for t in c] for c in captions]
         n = int(n_per_image)
@@ -222,13 +248,14 @@ class Pipeline:
                              f"more than max_seq_len - 1 = {T - 1}")
         # <start> ids <end> 0...: T + 1 columns, so that a caption of T - 1 tokens keeps its <end>
         tok = torch.from_numpy(pack_tokens(caps, T + 1, self.start_token, self.end_token, T)).to(images.device)
-        out = self.engine.eval_step(images, tok, n_per_image=n)
-        logp, ln = out["caption_logp"].cpu().tolist(), out["caption_len"].cpu().tolist()
+        with self._weights(weights):
+            out = self.engine.eval_step(images, tok, n_per_image=n)
+            logp, ln = out["caption_logp"].cpu().tolist(), out["caption_len"].cpu().tolist()
         return list(zip(logp, ln))
 
     # ------------------------------------------------------------ predict
     @torch.no_grad()
-    def predict(self, img, max_seq_len, plot_layer=False):
+    def predict(self, img, max_seq_len, plot_layer=False, weights="model"):
         """Reference beam procedure (pipeline.py:82-154) for one image (h, w, 3):
         BEAM_SEARCH_N beams through the HIP decode path (fpnmt.decode.
         BeamDecoder: K/V cache, on-device softmax / top-k / beam bookkeeping,
@@ -238,6 +265,9 @@ class Pipeline:
         decoder call (pipeline.py:109, kept for plot_attention_weights) is
         recomputed only when plot_layer is set: one transformer call on the
         identical beams' final prefix; None otherwise."""
+        if weights != "model":
+            with self._weights(weights):
+                return self.predict(img, max_seq_len, plot_layer)
         ids = self.predict_batch(img[None], max_seq_len, beam_n=BEAM_SEARCH_N)[0]
         out = torch.tensor(ids, dtype=torch.int32, device=img.device)
         attention_weights = None
@@ -254,7 +284,7 @@ class Pipeline:
     @torch.no_grad()
     def predict_batch(self, images, max_seq_len=None, beam_n=BEAM_SEARCH_N, use_graph=True, mode="reference",
                       length_alpha=0.0, n_best=1, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None,
-                      no_repeat_ngram=0, repetition_penalty=1.0, min_len=0, banned_tokens=()):
+                      no_repeat_ngram=0, repetition_penalty=1.0, min_len=0, banned_tokens=(), weights="model"):
         """predict() for a batch of images (n, h, w, 3) at once: the same
         beam procedure per image (pipeline.py:82-154), with a K/V cache and a
         hipGraph per decode step (fpnmt.decode.BeamDecoder). Returns one
@@ -283,7 +313,16 @@ class Pipeline:
         banned_tokens are never emitted. The returned scores are then
         log-probabilities under the constrained, renormalised distribution,
         and in sample mode the constraints come before temperature, top_k
-        and top_p."""
+        and top_p.
+
+        weights="ema" decodes on the averaged weights (Pipeline(ema_decay=
+        ...)); the decoders and their graphs are the ones weights="model"
+        uses."""
+        if weights != "model":
+            with self._weights(weights):
+                return self.predict_batch(images, max_seq_len, beam_n, use_graph, mode, length_alpha, n_best,
+                                          n_samples, temperature, top_k, top_p, seed, no_repeat_ngram,
+                                          repetition_penalty, min_len, banned_tokens)
         from fpnmt.decode import BeamDecoder, SampleDecoder
         T = max_seq_len or self.max_seq_len
         try:
@@ -312,13 +351,15 @@ class Pipeline:
         return dec.decode(images, n_best=n_best)
 
 
-    def evaluate(self, generator, max_seq_len):
+    def evaluate(self, generator, max_seq_len, weights="model"):
         """pipeline.py:156-175: caption every (img, imgId) of the generator ->
-        [{'image_id', 'caption'}] (the MetricEval results format)."""
+        [{'image_id', 'caption'}] (the MetricEval results format).
+        weights="ema": on the averaged weights, exchanged once around the loop."""
         results = []
-        for img, img_id in generator:
-            result = self.predict(img, max_seq_len)[0]
-            results.append({"image_id": img_id, "caption": self._to_text(result)})
+        with self._weights(weights):
+            for img, img_id in generator:
+                result = self.predict(img, max_seq_len)[0]
+                results.append({"image_id": img_id, "caption": self._to_text(result)})
         return results
 
     def evaluate_img(self, img, max_seq_len):

@@ -790,6 +790,42 @@ int fpnmt_amsgrad_step_groups(const fpnmt_adam_desc* d, int blk_first, int nbloc
                               const float* blk_part, const int32_t* seg_blk0, long long* step,
                               const fpnmt_seg_prep* preps, const fpnmt_seg_group* groups,
                               fpnmt_stream_t stream);
+/* Weight averaging: fpnmt_amsgrad_step_groups with a shadow array `ema` (fp32,
+ * the arena's layout) that follows the parameters inside the same kernel, in
+ * the manner of tf.train.ExponentialMovingAverage. Per element of a segment
+ * that is not frozen, after p has its new value:
+ *   e = fmaf(omd_t, p_new - e, e)
+ *   omd_t = debias ? fmaxf(one_minus_decay, 9 / (10 + t)) : one_minus_decay
+ * with t = iterations + 1: TF's decay_t = min(decay, (1 + t) / (10 + t)),
+ * written on 1 - decay so that nothing cancels. param, m, v, vhat and the
+ * compute copies are bit for bit those of the step without `ema`; e is one
+ * more streamed fp32 array (8 B per element per step), no launch is added.
+ * ema_desc is device-resident, 16 B, read once per block at execution time:
+ * values written into it (stream-ordered) between two replays of a captured
+ * launch take effect at the next replay. one_minus_decay is 1 - decay
+ * computed in double and rounded once. A frozen segment's e is neither read
+ * nor written; alignment gaps of `ema` are never touched. groups and preps
+ * may each be null (the plain step / no fused refresh).
+ * FPNMT_E_ARG: ema or ema_desc null, ema aliasing param / grad / m / v /
+ * vhat, otherwise as fpnmt_amsgrad_step_part.                                */
+typedef struct fpnmt_ema_desc {
+  float one_minus_decay;
+  int32_t debias;
+  int32_t reserved[2];
+} fpnmt_ema_desc;
+int fpnmt_amsgrad_step_ema(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
+                           const int32_t* blk_seg, const long long* blk_start, int block_elems,
+                           const long long* off, const int32_t* seg_flags, float* param,
+                           const float* grad, float* m, float* v, float* vhat, const float* sumsq,
+                           const float* blk_part, const int32_t* seg_blk0, long long* step,
+                           const fpnmt_seg_prep* preps, const fpnmt_seg_group* groups, float* ema,
+                           const fpnmt_ema_desc* ema_desc, fpnmt_stream_t stream);
+/* a[i] <-> b[i] for i < n, in place (the averaged weights under the model and
+ * back without moving a pointer; two swaps are the identity). float4 body
+ * when both pointers are 16-B aligned, scalar otherwise and for the last
+ * n % 4 elements. n == 0 is a no-op. FPNMT_E_ARG: n < 0, a null pointer with
+ * n > 0, overlapping buffers.                                                */
+int fpnmt_swap_f32(float* a, float* b, long long n, fpnmt_stream_t stream);
 
 /* ---- batched beam decode (BASELINE C5; utils/pipeline.py:82-154) --------
  * fpnmt_decode_attention: softmax(q k^T * scale) v for ONE query position per
