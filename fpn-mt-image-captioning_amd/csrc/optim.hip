@@ -201,7 +201,12 @@ __device__ __forceinline__ uint32_t prep_div_c(uint32_t q, const fpnmt_seg_prep&
 // 1 - decay and the TF debias switch: omd_t = max(1 - decay, 9 / (10 + t)),
 // i.e. decay_t = min(decay, (1 + t) / (10 + t)) written on 1 - decay so that
 // nothing cancels. Frozen segments return before the descriptor is read.
-template <bool PREP, bool GROUPS, bool EMA>
+// GUARD: gstate (32 B, device-resident, written by grad_norm_total_kernel of
+// this step, uniform per block) holds the step's verdict. A skipped step's
+// blocks return before any load of the arena, the norms or the prep table;
+// otherwise clip_factor (1.0 without a global clip: x * 1.0f is x) scales the
+// gradient when no per-tensor clip is set.
+template <bool PREP, bool GROUPS, bool EMA, bool GUARD>
 __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk, const int32_t* __restrict__ blk_seg,
                                               const long long* __restrict__ blk_start, int block_elems,
                                               const long long* __restrict__ off,
@@ -214,7 +219,8 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
                                               const fpnmt_seg_prep* __restrict__ preps,
                                               const fpnmt_seg_group* __restrict__ groups,
                                               float* __restrict__ ema,
-                                              const fpnmt_ema_desc* __restrict__ ema_desc, float& s_ss,
+                                              const fpnmt_ema_desc* __restrict__ ema_desc,
+                                              const fpnmt_guard_state* __restrict__ gstate, float& s_ss,
                                               unsigned short* s_prep) {
   const int seg = blk_seg[blk];
   float g_scale = 1.f, g_decay = 0.f;
@@ -223,6 +229,12 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
     if (gp.frozen) return;
     g_scale = gp.lr_scale;
     g_decay = gp.weight_decay;
+  }
+  float g_fac = 1.f;  // the global clip factor of this step
+  if constexpr (GUARD) {
+    const fpnmt_guard_state gs = *gstate;
+    if (gs.skipped) return;  // uniform over the grid: nothing is read, nothing written
+    g_fac = gs.clip_factor;
   }
   const bool sparse_norm = seg_flags && (seg_flags[seg] & 1);
   if (d.clipnorm > 0.f && !sparse_norm && threadIdx.x < 64) {
@@ -258,7 +270,7 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
   auto upd = [&](float gr, float& pi, float& mi, float& vi, float& hi) {
     gr *= d.grad_scale;
     // per element as TF rounds it: (t * clip) / max(norm, clip), not t * factor
-    const float g = d.clipnorm > 0.f ? (gr * d.clipnorm) / fmaxf(nrm, d.clipnorm) : gr;
+    const float g = d.clipnorm > 0.f ? (gr * d.clipnorm) / fmaxf(nrm, d.clipnorm) : (GUARD ? gr * g_fac : gr);
     if (sparse_form) {
       mi = mi * d.beta1 + g * (1.f - d.beta1);
       vi = vi * d.beta2 + (g * g) * (1.f - d.beta2);
@@ -413,7 +425,7 @@ __device__ __forceinline__ void amsgrad_block(const fpnmt_adam_desc& d, int blk,
 // one workgroup per arena block, or a persistent grid striding over them
 // (gridDim.x < nblocks: the early optimizer part, no compute-copy refresh,
 // sharing the CUs with a running backward)
-template <bool PREP, bool GROUPS, bool EMA>
+template <bool PREP, bool GROUPS, bool EMA, bool GUARD>
 __global__ __launch_bounds__(256) void amsgrad_kernel(fpnmt_adam_desc d, int blk_first, int nblocks,
                                                       const int32_t* __restrict__ blk_seg,
                                                       const long long* __restrict__ blk_start, int block_elems,
@@ -428,18 +440,71 @@ __global__ __launch_bounds__(256) void amsgrad_kernel(fpnmt_adam_desc d, int blk
                                                       const fpnmt_seg_prep* __restrict__ preps,
                                                       const fpnmt_seg_group* __restrict__ groups,
                                                       float* __restrict__ ema,
-                                                      const fpnmt_ema_desc* __restrict__ ema_desc) {
+                                                      const fpnmt_ema_desc* __restrict__ ema_desc,
+                                                      const fpnmt_guard_state* __restrict__ gstate) {
   __shared__ float s_ss;
   __shared__ unsigned short s_prep[PREP ? PREP_LDS : 1];
   for (int b = (int)blockIdx.x; b < nblocks; b += (int)gridDim.x) {
     if (b != (int)blockIdx.x) __syncthreads();  // the previous block's LDS reads are done
-    amsgrad_block<PREP, GROUPS, EMA>(d, blk_first + b, blk_seg, blk_start, block_elems, off, seg_flags, param, grad,
-                                     m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, groups, ema, ema_desc, s_ss,
-                                     s_prep);
+    amsgrad_block<PREP, GROUPS, EMA, GUARD>(d, blk_first + b, blk_seg, blk_start, block_elems, off, seg_flags, param,
+                                            grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, groups, ema,
+                                            ema_desc, gstate, s_ss, s_prep);
   }
 }
 
 __global__ void step_inc_kernel(long long* step) { *step += 1; }
+
+// The whole gradient's ||g||^2 from the per-block partials of sumsq_kernel and
+// the caller-supplied norms of bit0 segments, frozen segments left out: one
+// workgroup, thread i takes blocks i, i + 256, ... in order, then the wave
+// tree and the four waves' sums in a fixed order (no atomics: the same bits
+// on every run). A bit0 segment contributes once, at its first block; the
+// partials of its blocks and of frozen ones are never written and not read.
+__global__ __launch_bounds__(256) void grad_norm_total_kernel(int nblocks, const int32_t* __restrict__ blk_seg,
+                                                              const int32_t* __restrict__ seg_flags,
+                                                              const fpnmt_seg_group* __restrict__ groups,
+                                                              const float* __restrict__ sumsq,
+                                                              const float* __restrict__ blk_part,
+                                                              const int32_t* __restrict__ seg_blk0, float gs,
+                                                              const fpnmt_guard_desc* __restrict__ gdesc,
+                                                              fpnmt_guard_state* __restrict__ gstate) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int b = (int)threadIdx.x; b < nblocks; b += 256) {
+    const int seg = blk_seg[b];
+    if (groups && groups[seg].frozen) continue;
+    if (seg_flags && (seg_flags[seg] & 1)) {
+      if (b == seg_blk0[seg]) s += sumsq[seg] * gs * gs;
+    } else {
+      s += blk_part[b];
+    }
+  }
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float total = (red[0] + red[1]) + (red[2] + red[3]);
+    // Inf or NaN: all exponent bits set (a finite gradient whose squares
+    // overflow lands here too: its norm has no fp32 value)
+    const bool bad = (__float_as_uint(total) & 0x7f800000u) == 0x7f800000u;
+    const float clip = gdesc->global_clipnorm;
+    gstate->sumsq_total = total;
+    gstate->skipped = bad ? 1 : 0;
+    gstate->clip_factor = bad ? 0.f : (clip > 0.f ? clip / fmaxf(sqrtf(total), clip) : 1.f);
+  }
+}
+
+// the step counter and the guard's counters after a guarded step
+__global__ void guard_step_inc_kernel(long long* step, fpnmt_guard_state* gstate) {
+  if (gstate->skipped) {
+    gstate->n_skipped += 1;
+    gstate->consecutive += 1;
+  } else {
+    *step += 1;
+    gstate->n_applied += 1;
+    gstate->consecutive = 0;
+  }
+}
 
 // a <-> b in place: float4 body when both pointers are 16-B aligned (the
 // arenas are), scalar otherwise and for the last < 4 elements; grid-stride
@@ -557,7 +622,7 @@ static int amsgrad_launch(const fpnmt_adam_desc* d, int blk_first, int nblocks, 
                           float* m, float* v, float* vhat, const float* sumsq, const float* blk_part,
                           const int32_t* seg_blk0, long long* step, const fpnmt_seg_prep* preps,
                           const fpnmt_seg_group* groups, float* ema, const fpnmt_ema_desc* ema_desc,
-                          fpnmt_stream_t stream) {
+                          fpnmt_guard_state* gstate, fpnmt_stream_t stream) {
   if (!d || !step) return fail(FPNMT_E_ARG, "amsgrad: null");
   if (blk_first < 0 || max_grid < 0) return fail(FPNMT_E_ARG, "amsgrad: negative first block / grid");
   const int grid = max_grid > 0 ? std::min(nblocks, max_grid) : nblocks;
@@ -566,23 +631,33 @@ static int amsgrad_launch(const fpnmt_adam_desc* d, int blk_first, int nblocks, 
   if (preps && (!seg_blk0 || block_elems > 16384 || block_elems % 4096))
     return fail(FPNMT_E_ARG, "amsgrad_prep: needs seg_blk0 and block_elems a multiple of 4096 (<= 16384)");
   if (nblocks > 0) {
-#define FPNMT_AMSGRAD_LAUNCH(PREP, GROUPS, EMA)                                                                   \
-  hipLaunchKernelGGL((amsgrad_kernel<PREP, GROUPS, EMA>), dim3(grid), dim3(256), 0, S(stream), *d, blk_first,      \
-                     nblocks, blk_seg, blk_start, block_elems, off, seg_flags, param, grad, m, v, vhat, sumsq,     \
-                     blk_part, seg_blk0, step, PREP ? preps : (const fpnmt_seg_prep*)nullptr,                      \
+#define FPNMT_AMSGRAD_LAUNCH(PREP, GROUPS, EMA, GUARD)                                                            \
+  hipLaunchKernelGGL((amsgrad_kernel<PREP, GROUPS, EMA, GUARD>), dim3(grid), dim3(256), 0, S(stream), *d,          \
+                     blk_first, nblocks, blk_seg, blk_start, block_elems, off, seg_flags, param, grad, m, v, vhat, \
+                     sumsq, blk_part, seg_blk0, step, PREP ? preps : (const fpnmt_seg_prep*)nullptr,               \
                      GROUPS ? groups : (const fpnmt_seg_group*)nullptr, EMA ? ema : (float*)nullptr,               \
-                     EMA ? ema_desc : (const fpnmt_ema_desc*)nullptr)
-#define FPNMT_AMSGRAD_PICK(EMA)                                                                     \
-  if (groups) {                                                                                     \
-    if (preps) FPNMT_AMSGRAD_LAUNCH(true, true, EMA); else FPNMT_AMSGRAD_LAUNCH(false, true, EMA);   \
-  } else {                                                                                          \
-    if (preps) FPNMT_AMSGRAD_LAUNCH(true, false, EMA); else FPNMT_AMSGRAD_LAUNCH(false, false, EMA); \
+                     EMA ? ema_desc : (const fpnmt_ema_desc*)nullptr,                                              \
+                     GUARD ? gstate : (const fpnmt_guard_state*)nullptr)
+#define FPNMT_AMSGRAD_PICK(EMA, GUARD)                                                                            \
+  if (groups) {                                                                                                   \
+    if (preps) FPNMT_AMSGRAD_LAUNCH(true, true, EMA, GUARD); else FPNMT_AMSGRAD_LAUNCH(false, true, EMA, GUARD);   \
+  } else {                                                                                                        \
+    if (preps) FPNMT_AMSGRAD_LAUNCH(true, false, EMA, GUARD); else FPNMT_AMSGRAD_LAUNCH(false, false, EMA, GUARD); \
   }
-    if (ema) { FPNMT_AMSGRAD_PICK(true) } else { FPNMT_AMSGRAD_PICK(false) }
+    if (gstate) {
+      if (ema) { FPNMT_AMSGRAD_PICK(true, true) } else { FPNMT_AMSGRAD_PICK(false, true) }
+    } else {
+      if (ema) { FPNMT_AMSGRAD_PICK(true, false) } else { FPNMT_AMSGRAD_PICK(false, false) }
+    }
 #undef FPNMT_AMSGRAD_PICK
 #undef FPNMT_AMSGRAD_LAUNCH
   }
-  if (inc_step) hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, S(stream), step);
+  if (inc_step) {
+    if (gstate)
+      hipLaunchKernelGGL(guard_step_inc_kernel, dim3(1), dim3(1), 0, S(stream), step, gstate);
+    else
+      hipLaunchKernelGGL(step_inc_kernel, dim3(1), dim3(1), 0, S(stream), step);
+  }
   return check_launch("amsgrad");
 }
 
@@ -594,7 +669,7 @@ int fpnmt_amsgrad_step_part(const fpnmt_adam_desc* d, int blk_first, int nblocks
                             fpnmt_stream_t stream) {
   return amsgrad_launch(d, blk_first, nblocks, inc_step, max_grid, blk_seg, blk_start, block_elems, off, seg_flags,
                         param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, nullptr, nullptr, nullptr,
-                        stream);
+                        nullptr, stream);
 }
 
 int fpnmt_amsgrad_step_groups(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
@@ -606,7 +681,7 @@ int fpnmt_amsgrad_step_groups(const fpnmt_adam_desc* d, int blk_first, int nbloc
   if (!groups) return fail(FPNMT_E_ARG, "amsgrad_step_groups: null group table");
   return amsgrad_launch(d, blk_first, nblocks, inc_step, max_grid, blk_seg, blk_start, block_elems, off, seg_flags,
                         param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, groups, nullptr, nullptr,
-                        stream);
+                        nullptr, stream);
 }
 
 int fpnmt_amsgrad_step_ema(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
@@ -621,7 +696,53 @@ int fpnmt_amsgrad_step_ema(const fpnmt_adam_desc* d, int blk_first, int nblocks,
     return fail(FPNMT_E_ARG, "amsgrad_step_ema: ema aliases another array");
   return amsgrad_launch(d, blk_first, nblocks, inc_step, max_grid, blk_seg, blk_start, block_elems, off, seg_flags,
                         param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, groups, ema, ema_desc,
-                        stream);
+                        nullptr, stream);
+}
+
+int fpnmt_grad_norm_total(int nblocks, const int32_t* blk_seg, const int32_t* seg_flags,
+                          const fpnmt_seg_group* groups, const float* sumsq, const float* blk_part,
+                          const int32_t* seg_blk0, float grad_scale, const fpnmt_guard_desc* guard_desc,
+                          fpnmt_guard_state* guard_state, fpnmt_stream_t stream) {
+  if (!guard_desc || !guard_state) return fail(FPNMT_E_ARG, "grad_norm_total: null guard record");
+  if (nblocks < 0) return fail(FPNMT_E_ARG, "grad_norm_total: nblocks < 0");
+  if (nblocks > 0 && (!blk_seg || !blk_part || !seg_blk0 || !sumsq))
+    return fail(FPNMT_E_ARG, "grad_norm_total: needs blk_seg, blk_part, seg_blk0 and sumsq");
+  hipLaunchKernelGGL(grad_norm_total_kernel, dim3(1), dim3(256), 0, S(stream), nblocks, blk_seg, seg_flags, groups,
+                     sumsq, blk_part, seg_blk0, grad_scale, guard_desc, guard_state);
+  return check_launch("grad_norm_total");
+}
+
+int fpnmt_amsgrad_step_guard(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
+                             const int32_t* blk_seg, const long long* blk_start, int block_elems,
+                             const long long* off, const int32_t* seg_flags, float* param, const float* grad,
+                             float* m, float* v, float* vhat, const float* sumsq, const float* blk_part,
+                             const int32_t* seg_blk0, long long* step, const fpnmt_seg_prep* preps,
+                             const fpnmt_seg_group* groups, float* ema, const fpnmt_ema_desc* ema_desc,
+                             const fpnmt_guard_desc* guard_desc, fpnmt_guard_state* guard_state,
+                             fpnmt_stream_t stream) {
+  if (!guard_desc || !guard_state) return fail(FPNMT_E_ARG, "amsgrad_step_guard: null guard record");
+  if (!d) return fail(FPNMT_E_ARG, "amsgrad: null");
+  if ((ema != nullptr) != (ema_desc != nullptr))
+    return fail(FPNMT_E_ARG, "amsgrad_step_guard: ema and its descriptor go together");
+  if (ema && (ema == param || ema == m || ema == v || ema == vhat || ema == grad))
+    return fail(FPNMT_E_ARG, "amsgrad_step_guard: ema aliases another array");
+  if (d->clipnorm > 0.f) {
+    // the two clips are exclusive; the descriptor lives on the device, so the
+    // check costs a read-back and is left out of a captured launch
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(S(stream), &cap) != hipSuccess) return fail(FPNMT_E_HIP, "amsgrad_step_guard: capture query");
+    if (cap == hipStreamCaptureStatusNone) {
+      fpnmt_guard_desc host{};
+      if (hipMemcpyAsync(&host, guard_desc, sizeof(host), hipMemcpyDeviceToHost, S(stream)) != hipSuccess ||
+          hipStreamSynchronize(S(stream)) != hipSuccess)
+        return fail(FPNMT_E_HIP, "amsgrad_step_guard: descriptor read-back");
+      if (host.global_clipnorm > 0.f)
+        return fail(FPNMT_E_ARG, "amsgrad_step_guard: clipnorm (per tensor) and global_clipnorm are exclusive");
+    }
+  }
+  return amsgrad_launch(d, blk_first, nblocks, inc_step, max_grid, blk_seg, blk_start, block_elems, off, seg_flags,
+                        param, grad, m, v, vhat, sumsq, blk_part, seg_blk0, step, preps, groups, ema, ema_desc,
+                        guard_state, stream);
 }
 
 int fpnmt_swap_f32(float* a, float* b, long long n, fpnmt_stream_t stream) {

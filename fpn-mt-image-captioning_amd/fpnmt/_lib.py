@@ -145,6 +145,15 @@ class EmaDesc(C.Structure):
     _fields_ = [("one_minus_decay", C.c_float), ("debias", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class GuardDesc(C.Structure):
+    _fields_ = [("global_clipnorm", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class GuardState(C.Structure):
+    _fields_ = [("sumsq_total", C.c_float), ("clip_factor", C.c_float), ("skipped", C.c_int32),
+                ("consecutive", C.c_int32), ("n_skipped", C.c_longlong), ("n_applied", C.c_longlong)]
+
+
 P = C.c_void_p
 I = C.c_int
 LL = C.c_longlong
@@ -229,6 +238,9 @@ SIGNATURES = {
                                   P],
     "fpnmt_amsgrad_step_ema": [C.POINTER(AdamDesc), I, I, I, I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
                                P],
+    "fpnmt_grad_norm_total": [I, P, P, P, P, P, P, F, P, P, P],
+    "fpnmt_amsgrad_step_guard": [C.POINTER(AdamDesc), I, I, I, I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                 P, P, P, P],
     "fpnmt_swap_f32": [P, P, LL, P],
     "fpnmt_decode_attention": [I, I, I, I, I, F, P, LL, P, LL, LL, LL, LL, P, I, I, P, LL, P],
     "fpnmt_beam_step": [I, I, I, P, LL, P, P, P, I, I, P, P, I, I, P, P, I, P, P, P],

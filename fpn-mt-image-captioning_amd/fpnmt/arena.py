@@ -133,6 +133,62 @@ class EmaDesc:
         return float(t.view(torch.float32)[0]), int(t[1])
 
 
+def check_global_clipnorm(x, who="global_clipnorm"):
+    """A global clip norm as a finite float >= 0 (0: no clip, only the
+    guard); anything else, NaN and infinity included, is refused."""
+    try:
+        c = float(x)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who} must be a finite number >= 0, got {x!r}") from None
+    if not 0.0 <= c < math.inf:  # NaN fails both comparisons
+        raise ValueError(f"{who} must be a finite number >= 0, got {x!r}")
+    return c
+
+
+class StepGuard:
+    """The two device records of the guarded step: the 16-byte
+    fpnmt_guard_desc (global_clipnorm, written by the host) and the 32-byte
+    fpnmt_guard_state (written by the device: the step's ||g||^2, its clip
+    factor, whether it was skipped, and the counters). Both are allocated
+    once and the descriptor is only ever written in place (stream-ordered):
+    captured optimizer graphs hold the pointers and read the values of the
+    moment they replay."""
+
+    def __init__(self, device, global_clipnorm=0.0):
+        self.desc = torch.zeros(4, dtype=torch.int32, device=device)
+        self.state = torch.zeros(8, dtype=torch.int32, device=device)
+        self._i64 = self.state.view(torch.int64)  # [2] n_skipped, [3] n_applied
+        self.set(global_clipnorm)
+
+    def set(self, global_clipnorm):
+        self.global_clipnorm = check_global_clipnorm(global_clipnorm)
+        d = L.GuardDesc()
+        d.global_clipnorm = self.global_clipnorm
+        self.desc.copy_(torch.frombuffer(bytearray(bytes(d)), dtype=torch.int32))  # in place
+
+    @property
+    def skipped(self):
+        """This step's verdict as a device int32 scalar (a view of the
+        state: no copy, no synchronisation)."""
+        return self.state[2]
+
+    def set_counts(self, n_skipped, n_applied):
+        self._i64[2:4].copy_(torch.tensor([int(n_skipped), int(n_applied)], dtype=torch.int64))
+
+    def host(self):
+        """The state as the device holds it (one read-back)."""
+        t = self.state.cpu()
+        f, q = t.view(torch.float32), t.view(torch.int64)
+        return {"sumsq_total": float(f[0]), "clip_factor": float(f[1]), "skipped": int(t[2]),
+                "consecutive": int(t[3]), "n_skipped": int(q[2]), "n_applied": int(q[3])}
+
+    def stats(self):
+        """host() with grad_norm = sqrt(sumsq_total) in place of the sum."""
+        h = self.host()
+        ss = h.pop("sumsq_total")
+        return {"grad_norm": math.sqrt(ss) if ss >= 0.0 else float("nan"), **h}
+
+
 class ParamArena:
     def __init__(self, params, device, sparse_names=()):
         """params: ordered list of (name, nn.Parameter) — shared parameters
@@ -209,6 +265,29 @@ class ParamArena:
         self.preparers = []
         self.ema = None  # enable_ema(): the averaged parameters, this arena's layout
         self.ema_desc = None
+        self.guard = None  # enable_guard(): the records of the guarded step
+
+    # ----------------------------------------------------- the step guard
+    def enable_guard(self, global_clipnorm=0.0):
+        """Allocate the guard's two device records (StepGuard).
+        amsgrad_step(..., guard=True) then computes the norm of the whole
+        gradient on the device, skips the step when it is not finite and,
+        with global_clipnorm > 0, scales every gradient by
+        clip / max(||g||, clip) (Keras' global_clipnorm). Called again: the
+        new clip norm in place, the counters are kept."""
+        if self.guard is None:
+            self.guard = StepGuard(self.device, global_clipnorm)
+        else:
+            self.guard.set(global_clipnorm)
+        return self.guard
+
+    def set_global_clipnorm(self, x):
+        """A new global clip norm from the next step on, written into the
+        device descriptor in place (stream-ordered; no recapture). 0 turns
+        the clip off and keeps the guard."""
+        if self.guard is None:
+            raise ValueError("ParamArena: enable_guard() first")
+        self.guard.set(x)
 
     # ---------------------------------------------------- weight averaging
     def enable_ema(self, decay, debias=True):
@@ -284,7 +363,8 @@ class ParamArena:
         return self._seg_blk0_host[i]
 
     def amsgrad_step(self, lr_schedule, beta1=0.9, beta2=0.98, eps=1e-9, clipnorm=1.0, grad_scale=1.0,
-                     preps=None, blocks=None, inc_step=True, max_grid=0, groups=None, ema=False):
+                     preps=None, blocks=None, inc_step=True, max_grid=0, groups=None, ema=False,
+                     guard=False):
         """Keras AMSGrad + per-tensor clip_by_norm over the arena. preps: a
         device table of fpnmt_seg_prep (one per segment, layers.FusedPrep)
         whose non-null entries get their bf16 compute copies written by the
@@ -297,9 +377,31 @@ class ParamArena:
         flags; frozen segments at either end of the range are not launched.
         None: the plain entry points, as before. ema: the step through
         fpnmt_amsgrad_step_ema (with or without groups), which also advances
-        the shadow arena of enable_ema(); False: the entry points above."""
+        the shadow arena of enable_ema(); False: the entry points above.
+        guard: the step through fpnmt_amsgrad_step_guard (with or without
+        groups and ema) on the records of enable_guard(): always
+        fpnmt_grad_sumsq_*, whatever clipnorm is, then fpnmt_grad_norm_total,
+        then the guarded kernel. The step is one launch: blocks= must contain
+        every block that is not frozen and inc_step must be set (the total
+        covers the whole arena, and a step updated in parts cannot be
+        undone); clipnorm > 0 together with a global clip norm > 0 is
+        refused, as Keras refuses it."""
         if ema and self.ema is None:
             raise ValueError("ParamArena.amsgrad_step(ema=True): enable_ema() first")
+        if guard:
+            if self.guard is None:
+                raise ValueError("ParamArena.amsgrad_step(guard=True): enable_guard() first")
+            if not inc_step:
+                raise ValueError("ParamArena.amsgrad_step(guard=True): inc_step=False is a step in parts, "
+                                 "which the guard cannot skip as a whole")
+            if clipnorm > 0 and self.guard.global_clipnorm > 0:
+                raise ValueError("ParamArena.amsgrad_step(guard=True): clipnorm (per tensor) and global_clipnorm "
+                                 "are exclusive; pass clipnorm=0 with a global clip norm")
+            lo, hi = (0, self.nblocks) if groups is None else groups.trim(0, self.nblocks)
+            q0, q1 = (0, self.nblocks) if blocks is None else blocks
+            if hi > lo and not (q0 <= lo and hi <= q1):
+                raise ValueError(f"ParamArena.amsgrad_step(guard=True): blocks={(q0, q1)} leaves blocks that are not "
+                                 f"frozen outside (they span [{lo}, {hi}))")
         d = L.AdamDesc()
         d.beta1, d.beta2, d.eps, d.clipnorm = beta1, beta2, eps, clipnorm
         d.grad_scale = grad_scale
@@ -313,6 +415,30 @@ class ParamArena:
             d.sched_warm_pow = float(lr_schedule.warmup_steps ** -1.5)
         b0, b1 = (0, self.nblocks) if blocks is None else blocks
         s = L.stream_ptr()
+        if guard:
+            gt = None
+            if groups is not None:
+                b0, b1 = groups.trim(b0, b1)
+                gt = L.ptr(groups.table)
+            if b1 > b0:
+                if gt is not None:
+                    L.call("fpnmt_grad_sumsq_groups", b0, b1 - b0, max_grid, L.ptr(self.blk_seg),
+                           L.ptr(self.blk_start), BLOCK_ELEMS, L.ptr(self.seg_bounds), L.ptr(self.seg_flags), gt,
+                           L.ptr(self.grad), grad_scale, L.ptr(self.blk_part), s)
+                else:
+                    L.call("fpnmt_grad_sumsq_part", b0, b1 - b0, max_grid, L.ptr(self.blk_seg),
+                           L.ptr(self.blk_start), BLOCK_ELEMS, L.ptr(self.seg_bounds), L.ptr(self.seg_flags),
+                           L.ptr(self.grad), grad_scale, L.ptr(self.blk_part), s)
+            gd, gs = L.ptr(self.guard.desc), L.ptr(self.guard.state)
+            L.call("fpnmt_grad_norm_total", self.nblocks, L.ptr(self.blk_seg), L.ptr(self.seg_flags), gt,
+                   L.ptr(self.sumsq), L.ptr(self.blk_part), L.ptr(self.seg_blk0), grad_scale, gd, gs, s)
+            L.call("fpnmt_amsgrad_step_guard", d, b0, b1 - b0, 1, max_grid, L.ptr(self.blk_seg),
+                   L.ptr(self.blk_start), BLOCK_ELEMS, L.ptr(self.seg_bounds), L.ptr(self.seg_flags),
+                   L.ptr(self.flat), L.ptr(self.grad), L.ptr(self.m), L.ptr(self.v), L.ptr(self.vhat),
+                   L.ptr(self.sumsq), L.ptr(self.blk_part), L.ptr(self.seg_blk0), L.ptr(self.step),
+                   L.ptr(preps) if preps is not None else None, gt, L.ptr(self.ema) if ema else None,
+                   L.ptr(self.ema_desc.table) if ema else None, gd, gs, s)
+            return
         if ema:
             gt = None
             if groups is not None:

@@ -12,12 +12,19 @@ checkpoint holding
                                    keeps an average (TrainEngine(ema_decay=...))
   optimizer/iterations             Keras `iterations` (int64, drives the lr
                                    schedule and the bias correction)
+  optimizer/guard/{n_skipped,n_applied}
+                                   the step guard's counters (int64), when the
+                                   engine runs the guarded step
+                                   (TrainEngine(global_clipnorm= / skip_nonfinite=))
 keyed by parameter NAME, so a checkpoint restores into any arena ordering.
 The ema keys are optional under the same format tag: a checkpoint without
 them restored into an averaging engine starts the average at the restored
 parameters, and an engine without an average ignores them.
 Checkpoint.export_ema(path) writes a model-only file whose model/ tensors are
 the averaged ones, which any Pipeline loads for inference.
+The guard keys are optional too: a checkpoint without them restored into a
+guarded engine starts both counts at zero, and an engine without the guard
+ignores them and writes none.
 A small JSON index (`checkpoint`) in the directory lists the files, newest
 last, like TF's `checkpoint` state file.
 
@@ -66,6 +73,10 @@ class Checkpoint:
                 for slot, buf in slots:
                     out[f"optimizer/{slot}/{name}"] = buf[off:off + n].view(p.shape).detach().cpu().clone()
             out["optimizer/iterations"] = a.step.detach().cpu().clone()
+            if a.guard is not None:
+                h = a.guard.host()
+                for k in ("n_skipped", "n_applied"):
+                    out[f"optimizer/guard/{k}"] = torch.tensor([h[k]], dtype=torch.int64)
         return out
 
     def write(self, path):
@@ -150,6 +161,10 @@ class Checkpoint:
                     key = f"optimizer/ema/{name}"
                     if key in keys:
                         a.ema[off:off + p.numel()].copy_(f.get_tensor(key).reshape(-1))
+            if eng is not None and eng.arena.guard is not None:
+                n = [int(f.get_tensor(k).reshape(-1)[0]) if k in keys else 0
+                     for k in ("optimizer/guard/n_skipped", "optimizer/guard/n_applied")]
+                eng.arena.guard.set_counts(*n)
             self.save_counter = int(meta.get("save_counter", self.save_counter))
         for m in self.transformer.modules():  # frozen-BN folds read the restored statistics
             if hasattr(m, "refresh_bn") and getattr(m, "bn_scale", None) is not None:

@@ -53,7 +53,7 @@ from . import _lib as L
 from . import dist as fdist
 from . import layers as flayers
 from . import ops
-from .arena import ParamArena, check_ema_decay
+from .arena import ParamArena, check_ema_decay, check_global_clipnorm
 from .layers import group_param_order
 from . import param_groups as pgroups
 
@@ -61,7 +61,8 @@ from . import param_groups as pgroups
 class TrainEngine:
     def __init__(self, transformer, schedule, beta1=0.9, beta2=0.98, eps=1e-9, clipnorm=1.0, use_graph=True,
                  group=None, bucket_bytes=fdist.DEFAULT_BUCKET_BYTES, split_backward=None, bucket_dtype=None,
-                 sync_bn=True, label_smoothing=0.0, param_groups=None, ema_decay=None, ema_debias=True):
+                 sync_bn=True, label_smoothing=0.0, param_groups=None, ema_decay=None, ema_debias=True,
+                 global_clipnorm=None, skip_nonfinite=False):
         """param_groups: None runs the plain step (every trainable tensor at
         the schedule's rate, no decay: the reference's optimizer). A list of
         fpnmt.param_groups.ParamGroup (an empty one included) runs the same
@@ -83,7 +84,31 @@ class TrainEngine:
         ema_weights() puts the average under the model; set_ema_decay /
         reset_ema change it between steps. Under data parallelism every rank
         keeps its own average: the parameters are bitwise equal across ranks
-        after every step, so the averages are too, and nothing is exchanged."""
+        after every step, so the averages are too, and nothing is exchanged.
+
+        global_clipnorm / skip_nonfinite: either one turns the step guard on
+        (both at their defaults: the step launches what it launched before,
+        with the same bits). The optimizer tail then computes the norm of the
+        whole gradient on the device (fpnmt_grad_norm_total, after the
+        all-reduce under data parallelism, so every rank decides alike) and
+        the update goes through fpnmt_amsgrad_step_guard: a step whose
+        squared norm is not finite (an Inf or NaN anywhere in the gradient, or
+        finite values whose squares overflow fp32) is skipped on the device,
+        with no host round trip: parameters, m, v, vhat, the average, the
+        compute copies and `iterations` stay as they were, and the counters
+        of guard_stats() record it. `iterations` feeds the dropout keys, so
+        the step after a skipped one draws the masks the skipped one drew.
+        global_clipnorm > 0 also scales every gradient by
+        clip / max(||g||, clip), Keras' global_clipnorm
+        (tf.clip_by_global_norm); it always skips non-finite steps, since a
+        non-finite norm cannot be clipped against. It is exclusive with the
+        per-tensor clipnorm > 0, as in Keras, and the guard is exclusive with
+        fpnmt.config.early_update, which updates the transformer's segments
+        before the backward has produced the rest of the gradient.
+        set_global_clipnorm changes the clip between steps.
+        Limit: a skipped step's forward pass has already moved the BatchNorm
+        moving statistics (MobileNetV2 in training mode). They are buffers,
+        not in the arena, and are not rolled back."""
         from models.transformer import create_masks  # noqa: F401 (ensures import path)
         groups_in = pgroups.validate(param_groups) if param_groups is not None else None
         if not 0.0 <= float(label_smoothing) < 1.0:  # NaN fails both comparisons
@@ -91,6 +116,16 @@ class TrainEngine:
         self.label_smoothing = float(label_smoothing)
         if ema_decay is not None:
             ema_decay = check_ema_decay(ema_decay, "TrainEngine: ema_decay")
+        self.guard_on = global_clipnorm is not None or bool(skip_nonfinite)
+        if global_clipnorm is not None:
+            global_clipnorm = check_global_clipnorm(global_clipnorm, "TrainEngine: global_clipnorm")
+            if global_clipnorm > 0 and clipnorm > 0:
+                raise ValueError("TrainEngine: global_clipnorm and the per-tensor clipnorm are exclusive "
+                                 f"(got global_clipnorm={global_clipnorm!r}, clipnorm={clipnorm!r}); pass clipnorm=0")
+        if self.guard_on and fpnmt.config.early_update:
+            raise ValueError("TrainEngine: global_clipnorm / skip_nonfinite cannot be combined with "
+                             "fpnmt.config.early_update (the early part updates the transformer's segments "
+                             "before the whole gradient exists)")
         self.model = transformer
         self.schedule = schedule
         self.adam = dict(beta1=beta1, beta2=beta2, eps=eps, clipnorm=clipnorm)
@@ -178,6 +213,9 @@ class TrainEngine:
         self._ema_open = False
         if ema_decay is not None:
             self.arena.enable_ema(ema_decay, ema_debias)
+        # the step guard: its two records are allocated once, captured graphs hold them
+        if self.guard_on:
+            self.arena.enable_guard(global_clipnorm or 0.0)
         flayers.invalidate_weights()
         self.dtype = None
         self.use_graph = use_graph
@@ -373,6 +411,43 @@ class TrainEngine:
         if self._ema_open:
             raise RuntimeError(f"TrainEngine.{who} inside ema_weights(): the model holds the averaged weights")
 
+    # ------------------------------------------------------- the step guard
+    def _require_guard(self, who):
+        if self.arena.guard is None:
+            raise ValueError(f"TrainEngine.{who}: the engine was built without global_clipnorm / skip_nonfinite")
+
+    @property
+    def global_clipnorm(self):
+        """The global clip norm in force (0: the guard alone; None: no guard)."""
+        return self.arena.guard.global_clipnorm if self.arena.guard is not None else None
+
+    def set_global_clipnorm(self, x):
+        """A new global clip norm from the next step on (0: no clip, the
+        guard stays). Written into the device descriptor in place
+        (stream-ordered): the captured graphs are kept and the next replay
+        reads the new value, like set_ema_decay."""
+        self._require_guard("set_global_clipnorm")
+        x = check_global_clipnorm(x, "TrainEngine.set_global_clipnorm")
+        if x > 0 and self.adam["clipnorm"] > 0:
+            raise ValueError("TrainEngine.set_global_clipnorm: the engine clips per tensor "
+                             f"(clipnorm={self.adam['clipnorm']!r}); the two are exclusive")
+        self.arena.set_global_clipnorm(x)
+
+    def guard_stats(self):
+        """One read-back of the guard's device state: {"grad_norm" (the last
+        step's ||g|| over all trainable tensors, after grad_scale; inf or nan
+        on a skipped step), "clip_factor" (1 without a global clip, 0 on a
+        skipped step), "skipped" (the last step, 0 / 1), "consecutive"
+        (skipped steps in a row), "n_skipped", "n_applied"}."""
+        self._require_guard("guard_stats")
+        return self.arena.guard.stats()
+
+    @property
+    def step_skipped(self):
+        """The last step's verdict as a device int32 scalar (no
+        synchronisation); None without the guard."""
+        return self.arena.guard.skipped if self.arena.guard is not None else None
+
     # ------------------------------------------------------------ pieces
     def _one(self, loss):
         """The loss's seed gradient, kept across steps (loss.backward() would
@@ -425,6 +500,8 @@ class TrainEngine:
         ops.runtime.reset_sites()  # dropout sites numbered from the step's start
         ops.reset_grad_sums()
         zs = self._zero_grad_fork()
+        if self.guard_on and fpnmt.config.early_update:
+            raise ValueError("TrainEngine: fpnmt.config.early_update cannot be combined with the step guard")
         early = (self.world == 1 and fpnmt.config.early_update and self.arena.flat.is_cuda
                  and 0 < self.early_blocks < self.arena.nblocks)
         ops.runtime.on_transformer_grads = self._early_update if early else None
@@ -553,7 +630,8 @@ class TrainEngine:
                 skip = {id(m) for m in fp._mods
                         if self.arena.offsets[self.arena.index[id(m.kernel)]] >= self.split_at}
         self.arena.amsgrad_step(self.schedule, grad_scale=1.0 / self.world, preps=fp.table if fp else None,
-                                blocks=blocks, groups=self.seg_groups, ema=self.arena.ema is not None, **self.adam)
+                                blocks=blocks, groups=self.seg_groups, ema=self.arena.ema is not None,
+                                guard=self.guard_on, **self.adam)
         if self._frozen_layers:
             # frozen masters do not change: their (fresh) copies need no refresh
             skip = set(skip) | {i for i, m in self._frozen_layers.items() if m._gen == flayers._GEN[0]}

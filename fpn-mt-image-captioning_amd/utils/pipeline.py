@@ -57,7 +57,8 @@ class Pipeline:
                  image_size=IMAGE_INPUT_SIZE, n_layers=num_layers, backbone=None, rate=DROPOUT_RATE,
                  device="cuda", init=None, use_graph=True, clipnorm_mode=CLIPNORM_MODE, max_to_keep=100,
                  data_dir=DATADIR, data_type_val=DATATYPE_VAL, label_smoothing=0.0, param_groups=None,
-                 backbone_lr_scale=1.0, freeze=(), weight_decay=0.0, ema_decay=None, ema_debias=True):
+                 backbone_lr_scale=1.0, freeze=(), weight_decay=0.0, ema_decay=None, ema_debias=True,
+                 global_clipnorm=None, skip_nonfinite=False):
         """param_groups (a list of fpnmt.param_groups.ParamGroup), or the
         common cases by keyword: backbone_lr_scale (the CNN backbone at that
         fraction of the transformer's rate), freeze (a subset of {"backbone",
@@ -72,7 +73,25 @@ class Pipeline:
         ema_debias as in tf.train.ExponentialMovingAverage(num_updates=...));
         eval_step, validate, score_captions, predict_batch and evaluate then
         take weights="ema" to run on the averaged weights, and checkpoints
-        carry the average. None (the default): no average, the step as before."""
+        carry the average. None (the default): no average, the step as before.
+
+        global_clipnorm / skip_nonfinite turn the step guard on
+        (TrainEngine(global_clipnorm=..., skip_nonfinite=...)): a step whose
+        gradient holds an Inf or NaN, or whose squared norm overflows fp32, is
+        skipped on the device with no host round trip, and global_clipnorm >
+        0 clips the gradient by its norm over all tensors (Keras'
+        global_clipnorm). The global clip is exclusive with the reference's
+        per-tensor one: pass clipnorm_mode="none" with it, e.g.
+        Pipeline(clipnorm_mode="none", global_clipnorm=1.0). guard_stats()
+        reads the last step's gradient norm and the counters; checkpoints
+        carry the counters; train_loss leaves skipped steps out. A skipped
+        step's forward pass has already moved the BatchNorm moving statistics
+        (MobileNetV2): they are buffers, not parameters, and are not rolled
+        back. Both at their defaults: the step as before."""
+        if global_clipnorm is not None and float(global_clipnorm) > 0 and clipnorm_for(clipnorm_mode) > 0:
+            raise ValueError(f"Pipeline: global_clipnorm={global_clipnorm!r} with clipnorm_mode={clipnorm_mode!r}: "
+                             "the per-tensor clip and the global clip are exclusive (as in Keras); "
+                             "pass clipnorm_mode='none' with global_clipnorm")
         self.max_seq_len = max_seq_len
         self._metric_eval_src = (data_dir, data_type_val)
         self._metric_eval = None
@@ -97,7 +116,8 @@ class Pipeline:
                                   clipnorm=clipnorm_for(clipnorm_mode), use_graph=use_graph,
                                   label_smoothing=label_smoothing,  # not in the reference; 0: its one-hot loss
                                   param_groups=param_groups if param_groups is not None else recipe,
-                                  ema_decay=ema_decay, ema_debias=ema_debias)
+                                  ema_decay=ema_decay, ema_debias=ema_debias,
+                                  global_clipnorm=global_clipnorm, skip_nonfinite=skip_nonfinite)
         self.optimizer = self.engine
         self.train_loss = Mean(name="train_loss")  # pipeline.py:35
         self.checkpoint_path = checkpoint_path
@@ -141,11 +161,22 @@ class Pipeline:
         """Masked sparse CE from logits, mean over ALL positions (pipeline.py:50-57)."""
         return ops.MaskedXentFn.apply(pred, real)
 
+    def guard_stats(self):
+        """The step guard's telemetry (TrainEngine.guard_stats; one
+        read-back): grad_norm, clip_factor, skipped, consecutive, n_skipped,
+        n_applied. Needs global_clipnorm or skip_nonfinite."""
+        return self.engine.guard_stats()
+
     def train_step(self, img, caption_token):
         """pipeline.py:64-80: one optimizer step, then train_loss(loss)
-        (device-side running mean: no host synchronisation per step)."""
+        (device-side running mean: no host synchronisation per step). With
+        the step guard on, a skipped step's loss stays out of train_loss
+        (selected on the guard's device word, still without a read-back)."""
         loss = self.engine.step(img, caption_token)
-        self.train_loss(loss)
+        if self.engine.guard_on:
+            self.train_loss(loss, keep=1 - self.engine.step_skipped)
+        else:
+            self.train_loss(loss)
         return loss
 
     def train_step_scst(self, img, refs, n_samples=5, baseline="mean", reward=None, temperature=1.0, top_k=0,

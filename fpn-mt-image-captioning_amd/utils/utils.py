@@ -41,13 +41,21 @@ class Mean:
         self._total = None
         self._count = None
 
-    def __call__(self, value):
+    def __call__(self, value, keep=None):
+        """keep: None, or a device scalar; the values count only where it is
+        non-zero (selected, not multiplied: a NaN that is left out stays
+        out). Still no host synchronisation."""
         v = torch.as_tensor(value).detach().to(torch.float32).reshape(-1)
         if self._total is None or self._total.device != v.device:
             self._total = torch.zeros((), dtype=torch.float32, device=v.device)
             self._count = torch.zeros((), dtype=torch.float32, device=v.device)
-        self._total.add_(v.sum())
-        self._count.add_(float(v.numel()))
+        if keep is None:
+            self._total.add_(v.sum())
+            self._count.add_(float(v.numel()))
+        else:
+            k = keep.reshape(()) != 0
+            self._total.add_(torch.where(k, v.sum(), torch.zeros_like(self._total)))
+            self._count.add_(torch.where(k, float(v.numel()), 0.0).to(torch.float32))
         return self.result_tensor()
 
     update_state = __call__

@@ -820,6 +820,82 @@ int fpnmt_amsgrad_step_ema(const fpnmt_adam_desc* d, int blk_first, int nblocks,
                            const float* blk_part, const int32_t* seg_blk0, long long* step,
                            const fpnmt_seg_prep* preps, const fpnmt_seg_group* groups, float* ema,
                            const fpnmt_ema_desc* ema_desc, fpnmt_stream_t stream);
+/* Global-norm clipping and the non-finite step guard. Two device-resident
+ * records, both read or written at execution time only (values written
+ * stream-ordered between two replays of a captured launch take effect at the
+ * next replay):
+ *   fpnmt_guard_desc   16 B, written by the host. global_clipnorm > 0: every
+ *                      gradient is scaled by clip / max(||g||, clip) with
+ *                      ||g|| the norm over ALL trainable tensors (Keras
+ *                      global_clipnorm, tf.clip_by_global_norm); 0: no global
+ *                      clip, only the guard.
+ *   fpnmt_guard_state  32 B, written by the device (zero it once).
+ * fpnmt_grad_norm_total: one workgroup of 256 threads, launched after
+ * fpnmt_grad_sumsq_* of the same step over the whole arena (nblocks = all of
+ * its blocks). It sums, in a fixed order without atomics, for every segment
+ * that is not frozen (groups may be null: none is) its blocks' blk_part
+ * entries, or for a bit0 segment sumsq[seg] * grad_scale^2 once: exactly the
+ * ||g||^2 the per-tensor clip uses for that segment. Partials of frozen and
+ * of bit0 blocks, which fpnmt_grad_sumsq_* never writes, are not read. It
+ * writes
+ *   sumsq_total
+ *   skipped     = !isfinite(sumsq_total)
+ *   clip_factor = global_clipnorm > 0 ? clip / max(sqrtf(total), clip) : 1,
+ *                 computed once (0 on a skipped step)
+ * and leaves the counters alone. A FINITE gradient whose squares overflow
+ * fp32 (sumsq_total = +Inf) counts as non-finite: its norm cannot be
+ * represented, so the step is skipped.
+ * fpnmt_amsgrad_step_guard: fpnmt_amsgrad_step_ema's arguments plus the two
+ * records; groups, preps and ema / ema_desc (both or neither) may be null.
+ * Per block, after the frozen check, one uniform 32-B load of the state:
+ *   skipped != 0   the block returns before any load of param, grad, m, v,
+ *                  vhat, ema, the prep table or the norms; nothing is
+ *                  written, compute copies included.
+ *   otherwise      the existing step. With d->clipnorm <= 0 the gradient is
+ *                  g = grad * grad_scale * clip_factor (clip_factor is 1.0
+ *                  without a global clip, and x * 1.0f is x: every output is
+ *                  bit for bit the unguarded entry point's); with
+ *                  d->clipnorm > 0 the per-tensor clip runs as before.
+ * inc_step != 0 launches a guarded increment: on an applied step
+ * iterations += 1, n_applied += 1, consecutive = 0; on a skipped one
+ * n_skipped += 1, consecutive += 1 and `iterations` stays, so the step after
+ * a skipped one sees the counter (and the dropout keys derived from it) the
+ * skipped one saw.
+ * The block range and max_grid keep their meaning (frozen heads and tails are
+ * still trimmed), but the launched range MUST contain every block that is
+ * not frozen, and the step must be one launch with inc_step != 0: the total
+ * covers the whole arena, and a step updated in parts cannot be undone.
+ * FPNMT_E_ARG: a null record; ema without ema_desc or the reverse; ema
+ * aliasing another array; d->clipnorm > 0 together with global_clipnorm > 0
+ * (Keras makes the two exclusive as well). The last check reads the 16-B
+ * descriptor back (one stream synchronisation) and is made only when
+ * d->clipnorm > 0 and the stream is not capturing; in a captured launch the
+ * caller keeps the two exclusive, and the per-tensor clip takes precedence.
+ * Otherwise as fpnmt_amsgrad_step_part.                                     */
+typedef struct fpnmt_guard_desc {
+  float global_clipnorm;
+  int32_t reserved[3];
+} fpnmt_guard_desc;
+typedef struct fpnmt_guard_state {
+  float sumsq_total;   /* ||g||^2 of the last step, all trainable tensors */
+  float clip_factor;
+  int32_t skipped;     /* this step */
+  int32_t consecutive; /* skipped steps in a row, 0 after an applied one */
+  long long n_skipped;
+  long long n_applied;
+} fpnmt_guard_state;
+int fpnmt_grad_norm_total(int nblocks, const int32_t* blk_seg, const int32_t* seg_flags,
+                          const fpnmt_seg_group* groups, const float* sumsq, const float* blk_part,
+                          const int32_t* seg_blk0, float grad_scale, const fpnmt_guard_desc* guard_desc,
+                          fpnmt_guard_state* guard_state, fpnmt_stream_t stream);
+int fpnmt_amsgrad_step_guard(const fpnmt_adam_desc* d, int blk_first, int nblocks, int inc_step, int max_grid,
+                             const int32_t* blk_seg, const long long* blk_start, int block_elems,
+                             const long long* off, const int32_t* seg_flags, float* param,
+                             const float* grad, float* m, float* v, float* vhat, const float* sumsq,
+                             const float* blk_part, const int32_t* seg_blk0, long long* step,
+                             const fpnmt_seg_prep* preps, const fpnmt_seg_group* groups, float* ema,
+                             const fpnmt_ema_desc* ema_desc, const fpnmt_guard_desc* guard_desc,
+                             fpnmt_guard_state* guard_state, fpnmt_stream_t stream);
 /* a[i] <-> b[i] for i < n, in place (the averaged weights under the model and
  * back without moving a pointer; two swaps are the identity). float4 body
  * when both pointers are 16-B aligned, scalar otherwise and for the last
