@@ -2,6 +2,7 @@
 // implicit-GEMM convolution (fwd / bwd-data / bwd-filter) and attention
 // (QK^T -> masked row softmax -> PV, and its backward), plus error handling.
 #include "gemm_impl.h"
+#include "wide_plan.h"
 #include <cstdlib>
 #include <cstring>
 
@@ -232,8 +233,8 @@ int fpnmt_set_workspace(void* ws, long long bytes) {
 }
 
 int fpnmt_set_wide_cfg(int cfg) {
-  if (cfg != 0 && cfg != 6 && cfg != 10)
-    return fail(FPNMT_E_ARG, "set_wide_cfg: cfg must be 0 (automatic), 6 or 10, got " + std::to_string(cfg));
+  if (cfg != 0 && cfg != 6 && cfg != 10 && cfg != 12)
+    return fail(FPNMT_E_ARG, "set_wide_cfg: cfg must be 0 (automatic), 6, 10 or 12, got " + std::to_string(cfg));
   g_wide_cfg = cfg;
   return 0;
 }
@@ -568,11 +569,14 @@ static void set_group_geom(GemmGroup& g, int H, int W, int Ho, int Wo) {
   g.fd_Wo = make_fastdiv(Wo);
 }
 
-// Grouped launches that go to the pipelined kernel (one 128x256 tile per CU):
-// a level whose tiles would spill a few past a multiple of the CU count goes
-// to the next launch instead. P3 + P4 of the batch-32 step fill 245 of 256
-// CUs; adding P5..P7 made 260 tiles, i.e. a second full tile time for 4 tiles
-// (100 us per subnet conv instead of ~55).
+// Grouped launches that go to the pipelined kernel (one wide tile per CU):
+// the wide planner (wide_plan.h) breaks the level list into launches and, in
+// gemm_dispatch.h, picks each launch's M step from the same cost model. A
+// level whose 128-row tiles would spill a few past a multiple of the CU count
+// (P3 + P4 of the batch-32 step fill 245 of 256 CUs; P5..P7 make it 262: a
+// second full tile time for 6 tiles, 100 us per subnet conv instead of ~55)
+// either starts a launch of its own or, where that costs less, stays in one
+// launch of all the levels at the 144-row step (233 tiles, tile class 12).
 static int cu_count() {
   static const int n = [] {
     int dev = 0, v = 0;
@@ -583,11 +587,30 @@ static int cu_count() {
   }();
   return n;
 }
-static bool pipe_tail_break(int dtype, int n_out, int k_red, int c_in, long long tiles_now, long long m_level) {
-  if (dtype != FPNMT_BF16 || n_out < 256 || k_red % 64 || c_in % 64 || tiles_now == 0) return false;
-  const long long cus = cu_count();
-  const long long after = tiles_now + ((m_level + 127) / 128) * ((n_out + 255) / 256);
-  return (after + cus - 1) / cus > (tiles_now + cus - 1) / cus && after % cus != 0 && after % cus <= cus / 4;
+// How many of the levels rows[0..n) (output rows each, n <= MAX_GROUPS) the
+// launch that starts at the first one takes. Only launches the wide class can
+// get are planned (bf16, N >= 256, 64-channel K-tiles); the rest take them all.
+static int wide_launch_levels(int dtype, int n_out, int k_red, int c_in, const long long* rows, int n) {
+  if (dtype != FPNMT_BF16 || n_out < 256 || k_red % 64 || c_in % 64 || n < 2) return n;
+  const int f = forced_wide_cfg();
+  const WidePlan P = wide_plan_levels(rows, n, (n_out + 255) / 256, k_red >= 1024 || f == 12, cu_count(), f);
+  return P.n_launch > 0 ? P.levels[0] : n;
+}
+
+int fpnmt_plan_wide_levels(int n_levels, const long long* level_rows, int n_out, int k_red, int cus,
+                           int* launch_levels, int* launch_ms, long long* launch_tiles) {
+  if (n_levels < 0 || n_levels > MAX_GROUPS || (n_levels > 0 && !level_rows) || n_out <= 0 || k_red <= 0 || cus <= 0)
+    return fail(FPNMT_E_ARG, "plan_wide_levels: 0 .. " + std::to_string(MAX_GROUPS) +
+                                 " levels, positive n_out, k_red and cus");
+  for (int i = 0; i < n_levels; ++i)
+    if (level_rows[i] <= 0) return fail(FPNMT_E_ARG, "plan_wide_levels: a level without rows");
+  const WidePlan P = wide_plan_levels(level_rows, n_levels, (n_out + 255) / 256, k_red >= 1024, cus);
+  for (int i = 0; i < P.n_launch; ++i) {
+    if (launch_levels) launch_levels[i] = P.levels[i];
+    if (launch_ms) launch_ms[i] = P.ms[i];
+    if (launch_tiles) launch_tiles[i] = P.tiles[i];
+  }
+  return P.n_launch;
 }
 
 int fpnmt_conv2d_fwd_grouped(const fpnmt_conv_desc* d, int n_levels, const fpnmt_conv_level* lv,
@@ -619,15 +642,21 @@ int fpnmt_conv2d_fwd_grouped(const fpnmt_conv_desc* d, int n_levels, const fpnmt
     p.act_alpha = d->act_alpha;
     bool vec = d->c % V == 0 && aligned16(w_ohwi);
     int any_res = -1;
-    long long tiles_now = 0;
+    // the output rows of the next levels with any: the planner's launch takes `take` of them
+    long long rows[MAX_GROUPS];
+    int nrows = 0;
+    for (int j = i; j < n_levels && nrows < MAX_GROUPS; ++j) {
+      const int ho = conv_out(lv[j].h, d->pad_t, d->pad_b, d->r, d->stride_h);
+      const int wo = conv_out(lv[j].w, d->pad_l, d->pad_r, d->s, d->stride_w);
+      if (ho > 0 && wo > 0 && lv[j].n > 0 && d->k > 0) rows[nrows++] = (long long)lv[j].n * ho * wo;
+    }
+    const int take = wide_launch_levels(d->dtype, d->k, p.K, d->c, rows, nrows);
     for (; i < n_levels && p.ngroups < MAX_GROUPS; ++i) {
       const fpnmt_conv_level& L = lv[i];
       const int ho = conv_out(L.h, d->pad_t, d->pad_b, d->r, d->stride_h);
       const int wo = conv_out(L.w, d->pad_l, d->pad_r, d->s, d->stride_w);
       if (ho <= 0 || wo <= 0 || L.n <= 0 || d->k <= 0) continue;
-      const long long m_level = (long long)L.n * ho * wo;
-      if (pipe_tail_break(d->dtype, d->k, p.K, d->c, tiles_now, m_level)) break;
-      tiles_now += ((m_level + 127) / 128) * ((d->k + 255) / 256);
+      if (p.ngroups == take) break;
       if (!L.x || !L.y || !w_ohwi) return fail(FPNMT_E_ARG, "conv2d_fwd_grouped: null pointer");
       const int has_res = L.residual != nullptr;
       if (any_res >= 0 && any_res != has_res) return fail(FPNMT_E_ARG, "conv2d_fwd_grouped: residual on some levels only");
@@ -690,17 +719,22 @@ static int conv2d_bwd_data_grouped_impl(const fpnmt_conv_desc* d, int n_levels, 
       p.r_mask = act_in;
     }
     bool vec = d->k % V == 0 && aligned16(w_flip);
-    long long tiles_now = 0;
+    // the dx rows of the next levels with any dz: the planner's launch takes `take` of them
+    long long rows[MAX_GROUPS];
+    int nrows = 0;
+    for (int j = i; j < n_levels && nrows < MAX_GROUPS; ++j) {
+      const long long m_level = (long long)lv[j].n * lv[j].h * lv[j].w;
+      if (m_level * d->c > 0 && conv_out(lv[j].h, d->pad_t, d->pad_b, d->r, 1) > 0 &&
+          conv_out(lv[j].w, d->pad_l, d->pad_r, d->s, 1) > 0)
+        rows[nrows++] = m_level;
+    }
+    const int take = wide_launch_levels(d->dtype, d->c, p.K, d->k, rows, nrows);
     for (; i < n_levels && p.ngroups < MAX_GROUPS; ++i) {
       const fpnmt_conv_level& L = lv[i];
       if ((long long)L.n * L.h * L.w * d->c <= 0) continue;
       const int ho = conv_out(L.h, d->pad_t, d->pad_b, d->r, 1);
       const int wo = conv_out(L.w, d->pad_l, d->pad_r, d->s, 1);
-      if (ho > 0 && wo > 0) {
-        const long long m_level = (long long)L.n * L.h * L.w;
-        if (pipe_tail_break(d->dtype, d->c, p.K, d->k, tiles_now, m_level)) break;
-        tiles_now += ((m_level + 127) / 128) * ((d->c + 255) / 256);
-      }
+      if (ho > 0 && wo > 0 && p.ngroups == take) break;
       if (!L.y) return fail(FPNMT_E_ARG, "conv2d_bwd_data_grouped: null dx");
       if (ho <= 0 || wo <= 0) {
         if (!accumulate && zero_fill(L.y, (size_t)L.n * L.h * L.w * d->c * esz, S(stream)))

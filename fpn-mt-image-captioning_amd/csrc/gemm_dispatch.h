@@ -11,6 +11,7 @@
 #include "gemm_impl.h"
 #include "gemm_pipe.h"
 #include "gemm_skinny.h"
+#include "wide_plan.h"
 
 namespace fpnmt {
 
@@ -202,7 +203,7 @@ static int choose_cfg(int amode, int bmode, int M, int N, int K, long long batch
 // launch queued in a deferred region, run by a grouped launch, cfg 112 with
 // jobs= blocks= tile= of that launch)
 // The cfg= codes above the CFG_* tile configs. The three pipe routes add the
-// tile class (PipePlan::cfg, 0-11): 160 + 10 / 11 print the same number as
+// tile class (PipePlan::cfg, 0-12): 160 + 10 / 11 print the same number as
 // 170 + 0 / 1 and the c= field tells them apart.
 enum GemmRoute {
   ROUTE_PIPE_WG = 110,         // pipelined weight gradient, launched
@@ -427,7 +428,15 @@ static int launch_pipe_lw(GemmParams& p, int batch, int splits, hipStream_t s) {
 //     x 4 waves of 112 x 32) 43.5-44.2 us, 208x128 (2 loaders, 1 x 8 of 208 x
 //     16) 55.4-56.8 and 112x256 with 2 loaders (no zero rows) 47.8-48.4,
 //     although the first two move fewer L2 -> LDS bytes per CU.
-//     fpnmt_set_wide_cfg(6 | 10) forces one (A/B probes, the bitwise test).
+//     fpnmt_set_wide_cfg(6 | 10 | 12) forces one (A/B probes, the bitwise tests).
+//   * the heads' five levels as one launch (cfg 12: a 160x256 LDS image, 4
+//     loaders, 1 x 8 MFMA waves of 144 x 32, rows 144-159 fed the zero chunk;
+//     3 x 52 KB of ring): at a 144-row M step P3..P7 of the batch-32 step are
+//     175 + 44 + 11 + 2 + 1 = 233 tiles, one wave of blocks, where the 128-row
+//     step's 262 took P5..P7 to a launch of their own (124 blocks of 64x64, 14.4
+//     us for 6 % of the rows). Taken only by a launch merged across such a
+//     break; wide_plan.h holds the rule, its cost model and the measured tile
+//     times (profiles/heads_one_launch/tiles.txt).
 // the 112-row M step leaves fewer output rows per CU over the launch's waves of blocks (tiles bn wide)
 static bool m112_fewer_rows(const GemmParams& p, int batch, int bn) {
   const long long cus = cu_count_dispatch(), tn = (long long)cdiv(p.N, bn) * batch;
@@ -435,14 +444,27 @@ static bool m112_fewer_rows(const GemmParams& p, int batch, int bn) {
   return 112 * w112 < 128 * w128;
 }
 
+static_assert(WIDE_MAX_LEVELS == MAX_GROUPS, "wide_plan.h plans whole grouped launches");
+
+// The wide class's tile form: the planner's M step for this launch's levels
+// (wide_plan.h; a plain launch is one level). A grouped launch that the planner
+// would have broken (no caller makes one) keeps the 112 / 128 rule.
 static int wide_cfg(const GemmParams& p, int batch) {
   if (const int f = forced_wide_cfg()) return f;
-  return m112_fewer_rows(p, batch, 256) ? 10 : 6;
+  long long rows[MAX_GROUPS] = {p.M};
+  const bool grouped = p.ngroups > 0 && !p.group_k;
+  for (int g = 0; grouped && g < p.ngroups; ++g) rows[g] = p.groups[g].M;
+  const int n = grouped ? p.ngroups : 1;
+  const long long tn = (long long)cdiv(p.N, 256) * batch;
+  const WidePlan plan = wide_plan_levels(rows, n, tn, p.K >= 1024, cu_count_dispatch());
+  const int ms = plan.n_launch == 1 ? plan.ms[0] : wide_launch_ms(rows, n, tn, cu_count_dispatch(), false);
+  return ms == 144 ? 12 : ms == 112 ? 10 : 6;
 }
 
 static int pipe_cfg(const GemmParams& p, int batch) {
   const long long tiles_big = (long long)cdiv(p.M, 128) * cdiv(p.N, 256) * batch;
-  if (p.N >= 256 && p.K >= 1024 && tiles_big >= 192) return wide_cfg(p, batch);
+  // (class 12 forced: small shapes reach it too, for the bitwise tests)
+  if (p.N >= 256 && ((p.K >= 1024 && tiles_big >= 192) || forced_wide_cfg() == 12)) return wide_cfg(p, batch);
   const long long tiles = (long long)cdiv(p.M, 64) * cdiv(p.N, 64) * batch;
   const int nk = p.K / 64;
   if (p.R && nk < 8) return 0;
@@ -451,7 +473,7 @@ static int pipe_cfg(const GemmParams& p, int batch) {
     // the 128x128 loader tile at the same 112-row M step (cfg 11: 1 x 4 MFMA
     // waves of 112 x 32) where it leaves fewer rows per CU (res4's 3x3: 196
     // tiles at batch 64, 98 at 32); fpnmt_set_wide_cfg(6) keeps the 128-row
-    // step, 10 leaves this class automatic
+    // step, 10 / 12 leave this class automatic
     return forced_wide_cfg() != 6 && m112_fewer_rows(p, batch, 128) ? 11 : 7;
   }
   if (tiles < 1024 && nk >= 8) return 2;
@@ -459,7 +481,7 @@ static int pipe_cfg(const GemmParams& p, int batch) {
 }
 
 // The (operand mode, tile class) pairs a dispatch rule can return, the only
-// ones instantiated: pipe_cfg's 0 1 2 6 7 8 10 11 on A_IM2COL (convs, scatter
+// ones instantiated: pipe_cfg's 0 1 2 6 7 8 10 11 12 on A_IM2COL (convs, scatter
 // and tall-row reroutes); 3 and row_short_cfg's 5 8 9 on A_ROW; 4 (64x64,
 // 4-stage spread ring) nowhere. FPNMT_PIPE_ALL_CFGS (tools/fwd_bench.hip only,
 // never the library) instantiates every class for the tool's forced tiles.
@@ -468,7 +490,7 @@ constexpr bool pipe_cfg_built(int cfg) {
 #ifdef FPNMT_PIPE_ALL_CFGS
   return true;
 #endif
-  if (AM == A_IM2COL) return cfg == 0 || cfg == 1 || cfg == 2 || cfg == 6 || cfg == 7 || cfg == 8 || cfg == 10 || cfg == 11;
+  if (AM == A_IM2COL) return cfg == 0 || cfg == 1 || cfg == 2 || cfg == 6 || cfg == 7 || cfg == 8 || cfg == 10 || cfg == 11 || cfg == 12;
   if (AM == A_ROW) return cfg == 3 || cfg == 5 || cfg == 8 || cfg == 9;
   return false;
 }
@@ -490,6 +512,7 @@ static int launch_pipe_cfg(int cfg, GemmParams& p, int batch, int splits, hipStr
     FPNMT_PIPE_CASE(9, launch_pipe_lw<64, 32, 2, 2, AM, 2, 4>)
     FPNMT_PIPE_CASE(10, launch_pipe_lw<128, 256, 1, 8, AM, 4, 3, 112>)
     FPNMT_PIPE_CASE(11, launch_pipe_lw<128, 128, 1, 4, AM, 4, 3, 112>)
+    FPNMT_PIPE_CASE(12, launch_pipe_lw<160, 256, 1, 8, AM, 4, 3, 144>)
   }
 #undef FPNMT_PIPE_CASE
   return fail(FPNMT_E_UNSUPPORTED, "gemm: pipe tile class " + std::to_string(cfg) + " not instantiated for this operand mode");
@@ -592,8 +615,64 @@ static PipePlan pipe_plan(const GemmParams& p, int batch, int amode) {
   return pipe_plan_split(cfg, pipe_split_for(p, batch), p);
 }
 
+// A 144-row launch merged over the tail break(s) of its level groups (tile
+// class 12, wide_plan.h) computes what the launches it replaces computed, bit
+// for bit. The part before a break keeps its K order in any tile class. A
+// part that pipe_split_for would have split on its own (P5..P7 of the batch-32
+// heads: 124 tiles of 64x64 over 36 K-tiles, 3 splits) summed its K-tiles as S
+// fp32 partials added in split order, so its tiles here run the same S chains
+// into the same slabs (gemm_pipe_lw_kernel, BM = 160: GemmGroup::K = the chain
+// length, C = the group's slab rows) and the same gemm_splitk_reduce_kernel
+// finishes them. One such part per launch (p.c_split is its slab stride);
+// a second one, or slabs past the workspace, would run unchained.
+static inline int launch_wide_chained(GemmParams& p, hipStream_t s) {
+  long long rows[MAX_GROUPS];
+  for (int g = 0; g < p.ngroups; ++g) rows[g] = p.groups[g].M;
+  const long long tn = cdiv(p.N, 256), cus = cu_count_dispatch();
+  GemmParams q = p, red = p;
+  RowOffsets ro{};
+  int S = 1;
+  for (int i = 0; i < p.ngroups && S == 1;) {
+    const int e = wide_tail_end(rows, i, p.ngroups, tn, cus);
+    if (e - i < p.ngroups) {  // one of the launches this one replaces
+      GemmParams sub = p;
+      sub.ngroups = e - i;
+      sub.M = 0;
+      for (int g = i; g < e; ++g) {
+        sub.groups[g - i] = p.groups[g];
+        sub.M += p.groups[g].M;
+      }
+      const PipePlan sp = pipe_plan_split(12, pipe_split_for(sub, 1), sub);
+      if (sp.splits > 1) {
+        S = sp.splits;
+        q.c_split = (long long)sub.M * p.N;
+        for (int g = i, r = 0; g < e; ++g) {  // the groups' slab rows back to back (launch_ws_split)
+          ro.off[g - i] = r;
+          q.groups[g].C = g_split_ws.part + (long long)r * p.N;
+          q.groups[g].R = nullptr;
+          q.groups[g].K = sp.kt_per * 64;
+          r += p.groups[g].M;
+          ro.off[g - i + 1] = r;
+        }
+        red = sub;
+        red.A = sub.groups[0].A; red.C = sub.groups[0].C; red.R = sub.groups[0].R;
+      }
+    }
+    i = e;
+  }
+  const int st = launch_pipe_cfg<A_IM2COL>(12, q, 1, 1, s);
+  if (st || S == 1) return st;
+  const long long items = (long long)red.M * cdiv(red.N, 4);
+  hipLaunchKernelGGL((gemm_splitk_reduce_kernel<bf16>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, red,
+                     (const float*)g_split_ws.part, S, ro);
+  return check_launch("gemm_splitk_reduce_kernel");
+}
+
 template <int AM>
 static int launch_pipe_plan(const PipePlan& plan, GemmParams& p, int batch, hipStream_t s) {
+  if constexpr (AM == A_IM2COL) {
+    if (plan.cfg == 12 && plan.splits <= 1 && batch == 1 && p.ngroups > 1 && !p.group_k) return launch_wide_chained(p, s);
+  }
   if (plan.splits <= 1) return launch_pipe_cfg<AM>(plan.cfg, p, batch, 1, s);
   return launch_ws_split<bf16>(p, plan.splits, plan.kt_per * 64, s, [&](GemmParams& q) {
     return launch_pipe_cfg<AM>(plan.cfg, q, 1, plan.splits, s);  // split only at batch 1

@@ -678,10 +678,37 @@ __global__ __launch_bounds__(NT) void gemm_pipe_kernel(const GemmParams p) {
 // the loader lanes keep BM rows (rows MS .. BM-1 DMA the zero chunk and are
 // never read), so the tile count over M is cdiv(M, MS) — e.g. MS = 112 puts
 // the C2 P3 conv (M = 25088) on 224 tiles instead of 196 of a 256-CU chip.
+// The raw fp32 partial of one reduction chain into a split-K slab (rows of N
+// floats): what epilogue_direct16 stores for a launch_ws_split launch (no
+// bias / scale / activation, + 0.f as its bias-less add).
+template <int TM, int TN>
+__device__ __forceinline__ void slab_store16(f32x4 (&acc)[TM][TN], int row0, int col0, int M, int N, float* slab) {
+  const int lane = threadIdx.x & 63;
+  static_for<0, TN>([&](auto bc) {
+    constexpr int b = decltype(bc)::value;
+    const int col = col0 + b * 16 + 4 * (lane >> 4);
+    if (col >= N) return;
+    static_for<0, TM>([&](auto ac) {
+      constexpr int a = decltype(ac)::value;
+      const int row = row0 + a * 16 + (lane & 15);
+      if (row >= M) return;
+      const f32x4 v = acc[a][b];
+      *(f32x4*)(slab + (long long)row * N + col) = f32x4{v[0] + 0.f, v[1] + 0.f, v[2] + 0.f, v[3] + 0.f};
+    });
+  });
+}
+
+// BM = 160 (the 144-row class of a launch merged over several level groups,
+// gemm_dispatch.h launch_wide_chained): a group whose K (GemmGroup::K) is
+// shorter than the launch's runs its reduction as chains of K / 64 K-tiles,
+// each from a zero accumulator into fp32 slab `chain` of its C (rows of N
+// floats, p.c_split apart) with no epilogue — the partials of the split-K
+// launch that group had on its own, for the same ordered reduce to finish.
 template <int BM, int BN, int WM, int WN, int AM, int NLW, int STAGES, int MS = BM>
 __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_lw_kernel(const GemmParams p) {
   typedef bf16 T;
   constexpr int BK = 64, CPR = 8, ROWB = 128, MF = 16, KS = 32;
+  constexpr bool CHAINS = BM == 160;
   constexpr int NC = 64 * WM * WN, NL = 64 * NLW;
   constexpr int WTM = MS / WM, WTN = BN / WN, TM = WTM / MF, TN = WTN / MF;
   static_assert(TM >= 1 && TN >= 1 && TM * MF * WM == MS && TN * MF * WN == BN && MS <= BM,
@@ -708,6 +735,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_lw_kernel(cons
   int M = p.M;
   int gH = p.H, gW = p.W, gHo = p.Ho, gWo = p.Wo;
   FastDiv gfdHoWo = p.fd_HoWo, gfdWo = p.fd_Wo;
+  int chain_k = p.K;
   if (p.ngroups > 0) {  // m-grouped launch (shared B); static indices only (see gemm_pipe_kernel)
     GemmGroup G = p.groups[0];
 #pragma unroll
@@ -718,6 +746,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_lw_kernel(cons
     M = G.M;
     gH = G.H; gW = G.W; gHo = G.Ho; gWo = G.Wo;
     gfdHoWo = G.fd_HoWo; gfdWo = G.fd_Wo;
+    if constexpr (CHAINS) chain_k = G.K;
   }
   const int N = p.N, K = p.K;
   const int m0 = tmi * MS, n0 = tni * BN;
@@ -725,6 +754,7 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_lw_kernel(cons
   const int zo = z / p.batch_inner, zi = z - zo * p.batch_inner;
   const int kt0 = (int)blockIdx.y * (p.k_per_split / BK);
   const int nk = max(0, min(K / BK - kt0, p.k_per_split / BK));
+  const int chain = CHAINS ? max(1, chain_k / BK) : nk;  // K-tiles per chain; >= nk: one chain, the epilogue
   typedef __attribute__((address_space(3))) void lds_void;
 
   if (wave >= WM * WN) {  // ---- loader waves -------------------------------
@@ -847,6 +877,18 @@ __global__ __launch_bounds__(64 * (WM * WN + NLW)) void gemm_pipe_lw_kernel(cons
         for (int b = 0; b < TN; ++b)
           acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[ks & 1][b], fa[ks & 1][a], acc[a][b], 0, 0, 0);
     });
+    if constexpr (CHAINS) {
+      if (chain < nk && (t + 1 == nk || (t + 1) % chain == 0)) {  // block-uniform: this chain's partial is complete
+        slab_store16<TM, TN>(acc, m0 + wm * WTM, n0 + wn * WTN, M, N, (float*)Cp0 + (long long)(t / chain) * p.c_split);
+#pragma unroll
+        for (int a = 0; a < TM; ++a)
+#pragma unroll
+          for (int b = 0; b < TN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+  }
+  if constexpr (CHAINS) {
+    if (chain < nk) return;  // the ordered reduce runs the epilogue
   }
   const long long c_off = zo * p.c_so + zi * p.c_si + (long long)blockIdx.y * p.c_split;
   epilogue_direct16<TM, TN>(p, acc, m0 + wm * WTM, n0 + wn * WTN, M, N, (char*)Cp0, c_off, Rg0 != nullptr, rpre);

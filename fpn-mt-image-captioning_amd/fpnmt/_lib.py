@@ -167,6 +167,7 @@ SIGNATURES = {
     "fpnmt_set_workspace": [P, LL],
     "fpnmt_set_wide_cfg": [I],
     "fpnmt_get_wide_cfg": [],
+    "fpnmt_plan_wide_levels": [I, C.POINTER(LL), I, I, I, C.POINTER(I), C.POINTER(I), C.POINTER(LL)],
     "fpnmt_fill_zero": [P, LL, P],
     "fpnmt_fill_zero_grid": [P, LL, I, P],
     "fpnmt_defer_begin": [P, LL],

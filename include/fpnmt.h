@@ -90,12 +90,29 @@ int fpnmt_set_workspace(void* ws, long long bytes);
  * 0 (the default): chosen per launch by tile count. 6: the 128-row M step in
  * both classes (128x256 loader tile, cfg 6; 128x128 loader tile, cfg 7).
  * 10: the 112-row M step on the 128x256 tile (cfg 10); the 128x128 class stays
- * automatic. Every form computes the same bytes (tests/test_gpu_kernels.py:
- * test_conv_wide_tiles_bitwise); only the tiling differs. Any other value:
- * FPNMT_E_ARG, the setting unchanged. Callers reset it to 0 when done.
+ * automatic. 12: the 144-row M step on a 160x256 image (cfg 12) for every
+ * bf16 conv with N >= 256 and 64-channel K-tiles, whatever its tile count and
+ * K, and every grouped launch's levels in one launch; the 128x128 class is
+ * not reached. Every form computes the same bytes (tests/test_gpu_kernels.py:
+ * test_conv_wide_tiles_bitwise, tests/test_gpu_heads_one_launch.py); only the
+ * tiling differs. Any other value: FPNMT_E_ARG, the setting unchanged.
+ * Callers reset it to 0 when done.
  * fpnmt_get_wide_cfg: the current setting.                                  */
 int fpnmt_set_wide_cfg(int cfg);
 int fpnmt_get_wide_cfg(void);
+
+/* The launch plan of a grouped bf16 conv (fpnmt_conv2d_fwd_grouped,
+ * fpnmt_conv2d_bwd_data_grouped*) whose launches can take the wide tile
+ * class: level_rows[0 .. n_levels) are the levels' output rows (n_levels <=
+ * 6), n_out the GEMM's N (the output channels), k_red its K (r * s * c), cus
+ * the chip's CU count. Returns the number of launches L (< 0: FPNMT_E_ARG) and
+ * fills, per launch in level order, how many levels it takes, the M step of
+ * its tiles as a wide-class launch (112, 128 or 144 rows) and its tile count
+ * at that step; each out pointer holds n_levels entries or is NULL. Pure host
+ * arithmetic with the automatic setting of fpnmt_set_wide_cfg: no device is
+ * touched (csrc/wide_plan.h has the cost model).                            */
+int fpnmt_plan_wide_levels(int n_levels, const long long* level_rows, int n_out, int k_red, int cus,
+                           int* launch_levels, int* launch_ms, long long* launch_tiles);
 
 /* Deferred ordered reductions. Between fpnmt_defer_begin and
  * fpnmt_defer_flush, the ordered second passes of the fp32 gradient
