@@ -250,6 +250,7 @@ SIGNATURES = {
     "fpnmt_sample_step": [I, I, P, LL, F, I, F, ULL, P, P, P, P, P, I, I, I, P, P, P],
     "fpnmt_sample_uniform": [I, I, ULL, P, P, P],
     "fpnmt_logits_constrain": [I, I, P, LL, P, I, I, P, I, F, I, I, P, I, P],
+    "fpnmt_logits_ensemble": [I, I, I, PP, C.POINTER(LL), C.POINTER(F), I, P, P, LL, P],
     "fpnmt_ciderd_reward": [P, I, I, P, I, P, P, P, P, P],  # fpnmt_cider_tables*: fpnmt.cider_device.CiderTables
     "fpnmt_scst_pack": [I, I, I, P, P, P, I, P, P, P, I, I, I, P, I, P, P, P],
     "fpnmt_bn_stats": [I, LL, I, P, P, P, P, P, F, P],
@@ -304,6 +305,7 @@ lib = _load()
 E_ARG, E_UNSUPPORTED, E_HIP = -1, -2, -3  # include/fpnmt.h status codes
 SAMPLE_FILTER_MAX_VOCAB = 16384  # FPNMT_SAMPLE_FILTER_MAX_VOCAB
 CONSTRAIN_MAX_LEN, CONSTRAIN_MAX_BANNED = 1024, 4096  # FPNMT_CONSTRAIN_MAX_*
+ENSEMBLE_MAX = 8  # FPNMT_ENSEMBLE_MAX
 CIDER_MAX_LEN = 128  # FPNMT_CIDER_MAX_LEN
 SCST_MEAN, SCST_GREEDY = 0, 1  # FPNMT_SCST_*
 

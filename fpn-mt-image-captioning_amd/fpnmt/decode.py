@@ -46,6 +46,20 @@ sample: l_token - logsumexp(constrained l) — the log-probability under the
 constrained, renormalised distribution, and in sample mode the constraints
 come before temperature, top_k and top_p. With all four at their defaults no
 call is made and the graphs are launch for launch what they were.
+
+Ensemble decoding (all modes): `ensemble` names further Transformers that
+decode jointly with the main model. What belongs to one model (its geometry,
+K/V cache, cross K/V, staged biases) lives in a _Model record and the decoder
+holds a list of them, the main model first; tokens, history, cache-row tables,
+scores and `fin` stay per decoder, so every member sees the same tokens and
+tables. A step then runs every member's _logits one after another on the
+current stream, one fpnmt_logits_ensemble that folds the M rows into the
+first member's logits buffer ("prob": the log of the weighted mean of the
+distributions; "logprob": the weighted mean of the log-probabilities,
+renormalised by the step kernel), then the constraints, then the step kernel:
+scores are log-probabilities under the combined (and then constrained)
+distribution. With an empty `ensemble` the list holds the one model, no call
+is made and the graphs are launch for launch what they were.
 """
 from __future__ import annotations
 
@@ -67,29 +81,116 @@ def _gemm(m, n, k, dt, a, lda, b, c, ldc, bias, s):
     call("fpnmt_gemm", g, a, b, c, None, bias, None, s)
 
 
-class _CachedDecoder:
-    """What BeamDecoder and SampleDecoder share: the geometry, the encoder
-    pass with every layer's cross K/V, the staged biases, and one decode
-    position through embed -> layers -> fp32 logits on the K/V cache.
-    `beam_n` is the number of rows per image."""
+ENSEMBLE_MODES = {"prob": 0, "logprob": 1}  # fpnmt_logits_ensemble's mode
 
-    def __init__(self, transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph=True):
+
+def ensemble_weights_normalised(n_models, weights):
+    """One weight per model (the main model first) -> the tuple normalised to
+    sum 1 in fp64; None: equal weights. ValueError names a bad value."""
+    if weights is None:
+        return (1.0 / n_models,) * n_models
+    try:
+        w = [float(x) for x in weights]
+    except (TypeError, ValueError):
+        raise ValueError(f"ensemble_weights must be a sequence of numbers, got {weights!r}") from None
+    if len(w) != n_models:
+        raise ValueError(f"ensemble_weights: {len(w)} weights {weights!r} for {n_models} models (the main model first)")
+    for x in w:
+        if not (x > 0.0 and math.isfinite(x)):
+            raise ValueError(f"ensemble_weights must be finite positive numbers, got {x!r}")
+    total = math.fsum(w)
+    if not math.isfinite(total):
+        raise ValueError(f"ensemble_weights {weights!r}: their sum is not finite")
+    return tuple(x / total for x in w)
+
+
+class _Model:
+    """What belongs to ONE model of a decoder: the Transformer, its geometry,
+    and (filled by the decoder) its K/V cache `kv`, cross K/V `enc_kv` with
+    `Lenc`, and the staged `qkv_bias`."""
+
+    def __init__(self, transformer):
         self.tr = transformer
         dec = transformer.decoder
+        self.d = dec.d_model
+        self.L = dec.num_layers
+        self.heads = dec.dec_layers[0].mha1.num_heads if self.L else 8
+        self.depth = self.d // self.heads
+        self.kv = self.enc_kv = self.Lenc = None
+        self.qkv_bias = []
+
+
+class _CachedDecoder:
+    """What BeamDecoder and SampleDecoder share: the geometry, per model
+    (self.models, the one it was given first) the encoder pass with every
+    layer's cross K/V, the staged biases, and one decode position through
+    embed -> layers -> fp32 logits on the K/V cache; and the fold of several
+    models' logits into one row. `beam_n` is the number of rows per image."""
+
+    def __init__(self, transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph=True,
+                 ensemble=(), ensemble_mode="prob", ensemble_weights=None):
+        self.tr = transformer
         self.n_images, self.beam_n, self.T = n_images, beam_n, max_seq_len
         self.start_token, self.end_token = start_token, end_token
         self.R = n_images * beam_n
-        self.d = dec.d_model
-        self.L = dec.num_layers
         self.V = transformer.final_layer.kernel.shape[1]
-        self.heads = dec.dec_layers[0].mha1.num_heads if self.L else 8
-        self.depth = self.d // self.heads
-        if max_seq_len > dec.pos_encoding.shape[0]:
-            raise ValueError(f"max_seq_len {max_seq_len} exceeds the decoder's positional table")
+        self.models = [_Model(transformer)]
+        self._set_ensemble(ensemble, ensemble_mode, ensemble_weights)
+        for i, m in enumerate(self.models):
+            if max_seq_len > m.tr.decoder.pos_encoding.shape[0]:
+                raise ValueError(f"max_seq_len {max_seq_len} exceeds the decoder's positional table"
+                                 + (f" (ensemble member {i})" if i else ""))
         self.use_graph = use_graph
         self.dt = None
         self.graphs = None
-        self.qkv_bias = []
+
+    # ------------------------------------------------------------ ensemble
+    def _set_ensemble(self, ensemble, mode, weights):
+        """Validates the members, the mode and the weights; self.models gains
+        a record per member (the decoder holds them strongly)."""
+        members = tuple(ensemble)
+        if not members:
+            if mode != "prob" or weights is not None:
+                raise ValueError(f"ensemble_mode={mode!r} / ensemble_weights={weights!r} given with an empty ensemble")
+            self.ens_mode = self.ens_weights = None
+            return
+        if mode not in ENSEMBLE_MODES:
+            raise ValueError(f"ensemble_mode must be 'prob' or 'logprob', got {mode!r}")
+        n = 1 + len(members)
+        if n > L.ENSEMBLE_MAX:
+            raise ValueError(f"an ensemble holds at most {L.ENSEMBLE_MAX} models, got {n} (the main model and "
+                             f"{len(members)} members)")
+        dev = self.tr.final_layer.kernel.device
+        for i, tr in enumerate(members):
+            k = getattr(getattr(tr, "final_layer", None), "kernel", None)
+            if k is None:
+                raise ValueError(f"ensemble member {i + 1} is not a Transformer: {tr!r}")
+            if k.shape[1] != self.V:
+                raise ValueError(f"ensemble member {i + 1} has vocabulary {k.shape[1]}, the main model {self.V}")
+            if k.device != dev:
+                raise ValueError(f"ensemble member {i + 1} is on {k.device}, the main model on {dev}")
+        self.ens_weights = ensemble_weights_normalised(n, weights)
+        self.ens_mode = mode
+        self.models += [_Model(tr) for tr in members]
+
+    def _combine(self, logits):
+        """The members' fp32 logits (R, V), in self.models' order, folded into
+        the first one's buffer (fpnmt_logits_ensemble); finished rows, where
+        the decoder has a `fin`, are left alone."""
+        import ctypes as C
+        n = len(logits)
+        fin = getattr(self, "fin", None)  # mode="reference" has none: every row is combined
+        call("fpnmt_logits_ensemble", self.R, self.V, n, (C.c_void_p * n)(*[ptr(x) for x in logits]),
+             (C.c_longlong * n)(*[self.V] * n), (C.c_float * n)(*self.ens_weights), ENSEMBLE_MODES[self.ens_mode],
+             ptr(fin), ptr(logits[0]), self.V, stream_ptr())
+        return logits[0]
+
+    def _all_logits(self, t, src):
+        """Position t's logits row per decode row: the one model's, or the
+        fold of every member's."""
+        if len(self.models) == 1:
+            return self._logits(self.models[0], t, src)
+        return self._combine([self._logits(m, t, src) for m in self.models])
 
     # --------------------------------------------------------- constraints
     def _set_constraints(self, no_repeat_ngram, repetition_penalty, min_len, banned_tokens, need):
@@ -134,102 +235,106 @@ class _CachedDecoder:
              len(self.banned_tokens), stream_ptr())
 
     def _alloc_cache(self, dev):
-        self.kv = torch.empty((max(self.L, 1), self.R, self.T, 2 * self.d), dtype=self.dt, device=dev)
+        for m in self.models:
+            m.kv = torch.empty((max(m.L, 1), self.R, self.T, 2 * m.d), dtype=self.dt, device=dev)
         self.tok = torch.empty(self.R, dtype=torch.int32, device=dev)
 
     # ------------------------------------------------------------- encoder
-    def _encode(self, images):
-        """Encoder once per image (pipeline.py:93-94) and every layer's cross
-        K/V from one grouped GEMM (no per-beam tiling: the attention maps beam
-        rows to their image)."""
-        tr, dec = self.tr, self.tr.decoder
+    def _encode(self, m, images):
+        """Encoder of model m once per image (pipeline.py:93-94) and every
+        layer's cross K/V from one grouped GEMM (no per-beam tiling: the
+        attention maps beam rows to their image)."""
+        tr, dec = m.tr, m.tr.decoder
         enc = tr.encoder(images, False, None)  # (n, Lenc, d)
-        self.Lenc = enc.shape[1]
+        m.Lenc = enc.shape[1]
         n = enc.shape[0]
-        if self.L == 0:
-            self.enc_kv = torch.empty((1, 1), dtype=self.dt, device=enc.device)
+        if m.L == 0:
+            m.enc_kv = torch.empty((1, 1), dtype=self.dt, device=enc.device)
             return
         grp = dec.cross_kv_group
         stack, _ = grp.stacked(self.dt)
         cols = grp.n * grp.fout  # 2 * L * d
-        shape = (n * self.Lenc, cols)
-        if getattr(self, "enc_kv", None) is None or tuple(self.enc_kv.shape) != shape:
+        shape = (n * m.Lenc, cols)
+        if m.enc_kv is None or tuple(m.enc_kv.shape) != shape:
             # static buffer: the captured step graphs read it by address
-            self.enc_kv = torch.empty(shape, dtype=self.dt, device=enc.device)
+            m.enc_kv = torch.empty(shape, dtype=self.dt, device=enc.device)
             self.graphs = None
-        e2 = enc.reshape(n * self.Lenc, self.d).contiguous()
-        _gemm(n * self.Lenc, cols, self.d, dtype_code(self.dt), ptr(e2), self.d, ptr(stack), ptr(self.enc_kv), cols,
+        e2 = enc.reshape(n * m.Lenc, m.d).contiguous()
+        _gemm(n * m.Lenc, cols, m.d, dtype_code(self.dt), ptr(e2), m.d, ptr(stack), ptr(m.enc_kv), cols,
               ptr(grp.bias_cat()), stream_ptr())
 
-    def _stage_biases(self, dev):
-        """Each layer's [q|k|v] bias as one vector the step graphs read by
-        address: a view when the biases are adjacent (arena order), else a
-        static buffer refreshed here, once per decode call, instead of a
-        concatenation per layer inside every step."""
-        dec = self.tr.decoder
-        if len(self.qkv_bias) != self.L:
-            self.qkv_bias = [None] * self.L
+    def _stage_biases(self, m, dev):
+        """Each layer's [q|k|v] bias of model m as one vector the step graphs
+        read by address: a view when the biases are adjacent (arena order),
+        else a static buffer refreshed here, once per decode call, instead of
+        a concatenation per layer inside every step."""
+        dec = m.tr.decoder
+        if len(m.qkv_bias) != m.L:
+            m.qkv_bias = [None] * m.L
         for i, lay in enumerate(dec.dec_layers):
             b = lay.qkv_group.bias_cat()
-            cur = self.qkv_bias[i]
+            cur = m.qkv_bias[i]
             if b._base is not None or b.numel() == 0:  # a view of the parameters
                 if cur is None or cur.data_ptr() != b.data_ptr():
-                    self.qkv_bias[i] = b
+                    m.qkv_bias[i] = b
                     self.graphs = None
                 continue
             if cur is None or cur.shape != b.shape or cur._base is not None:
-                self.qkv_bias[i] = torch.empty_like(b, device=dev)
+                m.qkv_bias[i] = torch.empty_like(b, device=dev)
                 self.graphs = None
-            self.qkv_bias[i].copy_(b)
+            m.qkv_bias[i].copy_(b)
 
     def _prepare(self, images):
         """Before the first position of a decode call: buffers for the
-        compute dtype, the encoder side, the state reset, the step graphs."""
+        compute dtype, every model's encoder side, the state reset, the step
+        graphs."""
         dt = compute_dtype()
         if self.dt != dt:
             self.dt = dt
             self._alloc(images.device)
-            self.enc_kv = None
+            for m in self.models:
+                m.enc_kv = None
             self.graphs = None
-        self._encode(images)
-        self._stage_biases(images.device)
+        for m in self.models:
+            self._encode(m, images)
+            self._stage_biases(m, images.device)
         self._reset()
         if self.use_graph and self.graphs is None:
             self._capture()
 
     # ------------------------------------------------------------ position
-    def _logits(self, t, src):
-        """Position t of every row: embed self.tok, the decoder layers on the
-        K/V cache, the fp32 logits (R, V). src: the rows' cache-row tables
-        (None: every row reads its own cache row)."""
-        tr, dec = self.tr, self.tr.decoder
-        dt, code, R, T, d = self.dt, dtype_code(self.dt), self.R, self.T, self.d
+    def _logits(self, m, t, src):
+        """Position t of every row through model m: embed self.tok, the
+        decoder layers on m's K/V cache, the fp32 logits (R, V). src: the
+        rows' cache-row tables (None: every row reads its own cache row)."""
+        tr, dec = m.tr, m.tr.decoder
+        dt, code, R, T, d = self.dt, dtype_code(self.dt), self.R, self.T, m.d
         s = stream_ptr()
         x = torch.empty((R, d), dtype=dt, device=self.tok.device)
         pe = dec.pos_encoding
         call("fpnmt_embed_posenc_fwd", code, R, 1, d, ptr(self.tok), ptr(dec.embedding.embeddings),
              pe.data_ptr() + t * d * pe.element_size(), ptr(x), s)
-        scale = 1.0 / math.sqrt(float(self.depth))
+        scale = 1.0 / math.sqrt(float(m.depth))
         for i, lay in enumerate(dec.dec_layers):
             grp = lay.qkv_group
             stack, _ = grp.stacked(dt)
-            bias = self.qkv_bias[i]
+            bias = m.qkv_bias[i]
             q = torch.empty((R, d), dtype=dt, device=x.device)
             _gemm(R, d, d, code, ptr(x), d, ptr(stack), ptr(q), d, ptr(bias), s)
-            kvl = self.kv[i]
+            kvl = m.kv[i]
             # this position's key / value straight into the cache (row r, position t)
             _gemm(R, 2 * d, d, code, ptr(x), d, stack.data_ptr() + d * d * stack.element_size(),
                   kvl.data_ptr() + t * 2 * d * kvl.element_size(), T * 2 * d,
                   bias.data_ptr() + d * bias.element_size(), s)
             a = torch.empty((R, d), dtype=dt, device=x.device)
-            call("fpnmt_decode_attention", code, R, self.heads, self.depth, t + 1, scale, ptr(q), d, ptr(kvl),
+            call("fpnmt_decode_attention", code, R, m.heads, m.depth, t + 1, scale, ptr(q), d, ptr(kvl),
                  T * 2 * d, 2 * d, 0, d, ptr(src), T, 1, ptr(a), d, s)
             out1 = lay.layernorm1(lay.mha1.dense(a), residual=x)
             q2 = lay.mha2.wq(out1)
             a2 = torch.empty((R, d), dtype=dt, device=x.device)
-            cols = 2 * self.L * d
-            call("fpnmt_decode_attention", code, R, self.heads, self.depth, self.Lenc, scale, ptr(q2), d,
-                 ptr(self.enc_kv), self.Lenc * cols, cols, 2 * i * d, 2 * i * d + d, None, 0, self.beam_n, ptr(a2),
+            cols = 2 * m.L * d
+            call("fpnmt_decode_attention", code, R, m.heads, m.depth, m.Lenc, scale, ptr(q2), d,
+                 ptr(m.enc_kv), m.Lenc * cols, cols, 2 * i * d, 2 * i * d + d, None, 0, self.beam_n, ptr(a2),
                  d, s)
             out2 = lay.layernorm2(lay.mha2.dense(a2), residual=out1)
             x = lay.layernorm3(lay.ffn2(lay.ffn1(out2)), residual=out2)
@@ -257,22 +362,37 @@ class BeamDecoder(_CachedDecoder):
     live beam's logits row is constrained before the step ranks it, so a
     beam's score is the sum of log_softmax over the constrained rows — its
     log-probability under the constrained, renormalised distribution.
-    mode="reference" is the reference's own procedure and takes none."""
+    mode="reference" is the reference's own procedure and takes none.
+
+    ensemble: further Transformers that decode jointly with `transformer`
+    (at most ENSEMBLE_MAX models in all; any depth, width, heads and
+    backbone, the same vocabulary, device and a positional table that holds
+    max_seq_len). ensemble_mode "prob" (the default) ranks by the weighted
+    mean of the models' distributions, "logprob" by the renormalised weighted
+    mean of their log-probabilities; ensemble_weights: one positive number
+    per model, the main model first, normalised here (None: equal). Both
+    modes take an ensemble: "reference" then decodes greedily from the
+    combined distribution. The constraints come after the combine. A member
+    is another Transformer object and is NOT exchanged by weights="ema"; only
+    the main model is, and it shares storage with its own average: to
+    ensemble a model with its average, export_ema the average and load it as
+    a member (Pipeline.load_member)."""
 
     def __init__(self, transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph=True,
                  mode="reference", length_alpha=0.0, no_repeat_ngram=0, repetition_penalty=1.0, min_len=0,
-                 banned_tokens=()):
+                 banned_tokens=(), ensemble=(), ensemble_mode="prob", ensemble_weights=None):
         if mode not in ("reference", "beam"):
             raise ValueError(f"mode must be 'reference' or 'beam', got {mode!r}")
         self.mode, self.length_alpha = mode, float(length_alpha)
-        super().__init__(transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph)
+        super().__init__(transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph,
+                         ensemble, ensemble_mode, ensemble_weights)
         self._set_constraints(no_repeat_ngram, repetition_penalty, min_len, banned_tokens, beam_n)
         if self.constrained and mode != "beam":
             raise ValueError("constrained decoding needs mode='beam': mode='reference' is the reference's own procedure")
 
     # ---------------------------------------------------------- buffers
     def _alloc(self, dev):
-        dt, R, T, d = self.dt, self.R, self.T, self.d
+        R, T = self.R, self.T
         self._alloc_cache(dev)
         self.hist = [torch.empty((R, T + 1), dtype=torch.int32, device=dev) for _ in range(2)]
         self.src = [torch.empty((R, T), dtype=torch.int32, device=dev) for _ in range(2)]
@@ -310,7 +430,7 @@ class BeamDecoder(_CachedDecoder):
         s = stream_ptr()
         hin, hout = self.hist[t % 2], self.hist[(t + 1) % 2]
         sin, sout = self.src[t % 2], self.src[(t + 1) % 2]
-        logits = self._logits(t, sin)
+        logits = self._all_logits(t, sin)
         if self.mode == "beam":
             if self.constrained:
                 self._constrain(logits, hin, t)
@@ -380,11 +500,16 @@ class SampleDecoder(_CachedDecoder):
     and banned_tokens constrain every live row's logits before the draw, and
     so before temperature, top_k and top_p; the returned log-probability is
     then the sum of l_token - logsumexp(constrained l): the one under the
-    constrained, renormalised distribution."""
+    constrained, renormalised distribution.
+
+    ensemble, ensemble_mode, ensemble_weights: as for BeamDecoder; the draw
+    is from the combined distribution (then the constraints, then
+    temperature, top_k and top_p) and the log-probability is the one under
+    it."""
 
     def __init__(self, transformer, n_images, n_samples, max_seq_len, start_token, end_token, use_graph=True,
                  temperature=1.0, top_k=0, top_p=1.0, no_repeat_ngram=0, repetition_penalty=1.0, min_len=0,
-                 banned_tokens=()):
+                 banned_tokens=(), ensemble=(), ensemble_mode="prob", ensemble_weights=None):
         if n_samples < 1:
             raise ValueError(f"n_samples must be >= 1, got {n_samples}")
         if not (temperature > 0.0 and math.isfinite(temperature)):
@@ -396,7 +521,8 @@ class SampleDecoder(_CachedDecoder):
         if max_seq_len > 65536:
             raise ValueError(f"max_seq_len {max_seq_len}: the draw counter holds positions below 65536")
         self.temperature, self.top_k, self.top_p = float(temperature), int(top_k), float(top_p)
-        super().__init__(transformer, n_images, n_samples, max_seq_len, start_token, end_token, use_graph)
+        super().__init__(transformer, n_images, n_samples, max_seq_len, start_token, end_token, use_graph,
+                         ensemble, ensemble_mode, ensemble_weights)
         filtered = 0 < self.top_k < self.V or self.top_p < 1.0
         if filtered and self.V > L.SAMPLE_FILTER_MAX_VOCAB:
             raise ValueError(f"top_k / top_p need a vocabulary of at most {L.SAMPLE_FILTER_MAX_VOCAB}, got {self.V}")
@@ -421,7 +547,7 @@ class SampleDecoder(_CachedDecoder):
         self.fin.zero_()
 
     def _step(self, t):
-        logits = self._logits(t, None)
+        logits = self._all_logits(t, None)
         if self.constrained:
             self._constrain(logits, self.hist, t)
         call("fpnmt_sample_step", self.R, self.V, ptr(logits), self.V, self.temperature, self.top_k, self.top_p, 0,

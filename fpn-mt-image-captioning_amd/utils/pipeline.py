@@ -106,6 +106,7 @@ class Pipeline:
                 target_vocab_size = len(wi)
         self.target_vocab_size = target_vocab_size or TOP_K
         input_vocab_size = math.ceil(image_size / 16) ** 2  # pipeline.py:20
+        self._arch = dict(n_layers=n_layers, backbone=backbone, input_vocab_size=input_vocab_size)  # load_member
         self.transformer = Transformer(n_layers, d_model, num_heads, dff, input_vocab_size, self.target_vocab_size,
                                        rate, max_seq_len=self.max_seq_len, backbone=backbone, init=init).to(device)
         self.learning_rate = CustomSchedule(dff, WARM_UP_STEPS)  # pipeline.py:29 (d_model arg = dff)
@@ -286,7 +287,8 @@ class Pipeline:
 
     # ------------------------------------------------------------ predict
     @torch.no_grad()
-    def predict(self, img, max_seq_len, plot_layer=False, weights="model"):
+    def predict(self, img, max_seq_len, plot_layer=False, weights="model", ensemble=(), ensemble_mode="prob",
+                ensemble_weights=None):
         """Reference beam procedure (pipeline.py:82-154) for one image (h, w, 3):
         BEAM_SEARCH_N beams through the HIP decode path (fpnmt.decode.
         BeamDecoder: K/V cache, on-device softmax / top-k / beam bookkeeping,
@@ -295,11 +297,16 @@ class Pipeline:
         attention weights). The attention-weight dict of the reference's last
         decoder call (pipeline.py:109, kept for plot_attention_weights) is
         recomputed only when plot_layer is set: one transformer call on the
-        identical beams' final prefix; None otherwise."""
+        identical beams' final prefix (the main model's weights only, also
+        under an ensemble); None otherwise. ensemble, ensemble_mode,
+        ensemble_weights: as in predict_batch (the greedy decode from the
+        combined distribution)."""
         if weights != "model":
             with self._weights(weights):
-                return self.predict(img, max_seq_len, plot_layer)
-        ids = self.predict_batch(img[None], max_seq_len, beam_n=BEAM_SEARCH_N)[0]
+                return self.predict(img, max_seq_len, plot_layer, ensemble=ensemble, ensemble_mode=ensemble_mode,
+                                    ensemble_weights=ensemble_weights)
+        ids = self.predict_batch(img[None], max_seq_len, beam_n=BEAM_SEARCH_N, ensemble=ensemble,
+                                 ensemble_mode=ensemble_mode, ensemble_weights=ensemble_weights)[0]
         out = torch.tensor(ids, dtype=torch.int32, device=img.device)
         attention_weights = None
         if plot_layer:
@@ -315,7 +322,8 @@ class Pipeline:
     @torch.no_grad()
     def predict_batch(self, images, max_seq_len=None, beam_n=BEAM_SEARCH_N, use_graph=True, mode="reference",
                       length_alpha=0.0, n_best=1, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None,
-                      no_repeat_ngram=0, repetition_penalty=1.0, min_len=0, banned_tokens=(), weights="model"):
+                      no_repeat_ngram=0, repetition_penalty=1.0, min_len=0, banned_tokens=(), weights="model",
+                      ensemble=(), ensemble_mode="prob", ensemble_weights=None):
         """predict() for a batch of images (n, h, w, 3) at once: the same
         beam procedure per image (pipeline.py:82-154), with a K/V cache and a
         hipGraph per decode step (fpnmt.decode.BeamDecoder). Returns one
@@ -348,12 +356,32 @@ class Pipeline:
 
         weights="ema" decodes on the averaged weights (Pipeline(ema_decay=
         ...)); the decoders and their graphs are the ones weights="model"
-        uses."""
+        uses.
+
+        ensemble (all three modes): further models, Transformers or
+        Pipelines (their .transformer), that decode jointly with this one on
+        the device, at most fpnmt._lib.ENSEMBLE_MAX models in all; they may
+        differ in depth, width, heads and backbone and must share the
+        vocabulary and the device. Every position runs each member's decoder
+        on the shared tokens and one fpnmt_logits_ensemble folds their logits
+        rows: ensemble_mode "prob" into the log of the weighted mean of their
+        distributions, "logprob" into the weighted mean of their
+        log-probabilities (renormalised by the step). ensemble_weights: one
+        positive number per model, this pipeline's first, normalised to sum
+        1 (None: equal). Constraints apply to the combined row, and scores
+        are log-probabilities under the combined (constrained) distribution;
+        mode="reference" decodes greedily from it. ensemble_mode or
+        ensemble_weights with an empty ensemble raise ValueError. The
+        decoder keeps its members alive. weights="ema" exchanges this
+        pipeline's model only, never a member; a model and its own average
+        share storage, so to ensemble the two, export_ema the average and
+        load_member it."""
         if weights != "model":
             with self._weights(weights):
                 return self.predict_batch(images, max_seq_len, beam_n, use_graph, mode, length_alpha, n_best,
                                           n_samples, temperature, top_k, top_p, seed, no_repeat_ngram,
-                                          repetition_penalty, min_len, banned_tokens)
+                                          repetition_penalty, min_len, banned_tokens, ensemble=ensemble,
+                                          ensemble_mode=ensemble_mode, ensemble_weights=ensemble_weights)
         from fpnmt.decode import BeamDecoder, SampleDecoder
         T = max_seq_len or self.max_seq_len
         try:
@@ -363,39 +391,77 @@ class Pipeline:
         cons = dict(no_repeat_ngram=no_repeat_ngram, repetition_penalty=repetition_penalty, min_len=min_len,
                     banned_tokens=banned)
         ckey = (no_repeat_ngram, repetition_penalty, min_len, banned)
+        members = tuple(getattr(m, "transformer", m) for m in ensemble)
+        ens = dict(ensemble=members, ensemble_mode=ensemble_mode, ensemble_weights=ensemble_weights)
+        ekey = ()
+        if not members and (ensemble_mode != "prob" or ensemble_weights is not None):
+            # checked here too: a decoder cached under the plain key would not see the arguments
+            raise ValueError(f"ensemble_mode={ensemble_mode!r} / ensemble_weights={ensemble_weights!r} given with "
+                             "an empty ensemble")
+        if members:  # without members every decoder keeps the key it always had
+            from fpnmt.decode import ensemble_weights_normalised
+            ekey = ("ensemble", tuple(id(m) for m in members), ensemble_mode,
+                    ensemble_weights_normalised(1 + len(members), ensemble_weights))
         if mode == "sample":
             key = (images.shape[0], n_samples, T, use_graph, mode, float(temperature), top_k, float(top_p)) + ckey
+            key += ekey
             dec = getattr(self, "_decoders", {}).get(key)
             if dec is None:
                 dec = SampleDecoder(self.transformer, images.shape[0], n_samples, T, self.start_token, self.end_token,
-                                    use_graph=use_graph, temperature=temperature, top_k=top_k, top_p=top_p, **cons)
+                                    use_graph=use_graph, temperature=temperature, top_k=top_k, top_p=top_p, **cons,
+                                    **ens)
                 self.__dict__.setdefault("_decoders", {})[key] = dec
             return dec.decode(images, seed=seed)
         key = (images.shape[0], beam_n, T, use_graph, mode, float(length_alpha))
         if ckey != (0, 1.0, 0, ()):  # an unconstrained decoder keeps the key it always had
             key += ckey
+        key += ekey
         dec = getattr(self, "_decoders", {}).get(key)
         if dec is None:
             dec = BeamDecoder(self.transformer, images.shape[0], beam_n, T, self.start_token, self.end_token,
-                              use_graph=use_graph, mode=mode, length_alpha=length_alpha, **cons)
+                              use_graph=use_graph, mode=mode, length_alpha=length_alpha, **cons, **ens)
             self.__dict__.setdefault("_decoders", {})[key] = dec
         return dec.decode(images, n_best=n_best)
 
+    def load_member(self, path, n_layers=None, backbone=None, rate=0.0):
+        """A model-only checkpoint (ckpt.write / ckpt.export_ema of any
+        pipeline with this vocabulary) as an ensemble member: a bare
+        Transformer with this pipeline's vocabulary, max_seq_len and image
+        size, on this pipeline's device, restored with
+        Checkpoint(transformer).restore(path). n_layers / backbone not given:
+        this pipeline's. No TrainEngine and no optimizer state are created;
+        restore prepares the compute copies. Pass the result in
+        predict_batch(..., ensemble=[member])."""
+        arch = self._arch
+        if n_layers is None:
+            n_layers = arch["n_layers"]
+        if backbone is None:
+            backbone = arch["backbone"]
+        dev = self.transformer.final_layer.kernel.device
+        member = Transformer(n_layers, d_model, num_heads, dff, arch["input_vocab_size"], self.target_vocab_size,
+                             rate, max_seq_len=self.max_seq_len, backbone=backbone).to(dev)
+        Checkpoint(transformer=member).restore(path)
+        return member
 
-    def evaluate(self, generator, max_seq_len, weights="model"):
+    def evaluate(self, generator, max_seq_len, weights="model", ensemble=(), ensemble_mode="prob",
+                 ensemble_weights=None):
         """pipeline.py:156-175: caption every (img, imgId) of the generator ->
         [{'image_id', 'caption'}] (the MetricEval results format).
-        weights="ema": on the averaged weights, exchanged once around the loop."""
+        weights="ema": on the averaged weights, exchanged once around the loop.
+        ensemble, ensemble_mode, ensemble_weights: as in predict_batch."""
         results = []
         with self._weights(weights):
             for img, img_id in generator:
-                result = self.predict(img, max_seq_len)[0]
+                result = self.predict(img, max_seq_len, ensemble=ensemble, ensemble_mode=ensemble_mode,
+                                      ensemble_weights=ensemble_weights)[0]
                 results.append({"image_id": img_id, "caption": self._to_text(result)})
         return results
 
-    def evaluate_img(self, img, max_seq_len):
-        """pipeline.py:177-193."""
-        result = self.predict(img, max_seq_len)[0]
+    def evaluate_img(self, img, max_seq_len, ensemble=(), ensemble_mode="prob", ensemble_weights=None):
+        """pipeline.py:177-193. ensemble, ensemble_mode, ensemble_weights: as
+        in predict_batch."""
+        result = self.predict(img, max_seq_len, ensemble=ensemble, ensemble_mode=ensemble_mode,
+                              ensemble_weights=ensemble_weights)[0]
         return [{"image_id": 0, "caption": self._to_text(result)}]
 
     def _to_text(self, ids):

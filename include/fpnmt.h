@@ -24,6 +24,7 @@
  *   fpnmt_sample_step, fpnmt_sample_uniform    sampled decoding (temperature, top-k, top-p)    not in the reference
  *   fpnmt_logits_constrain                     n-gram blocking, repetition penalty, min length  not in the reference
  *   fpnmt_ciderd_reward, fpnmt_scst_pack       CIDEr-D reward and advantages on the device     not in the reference
+ *   fpnmt_logits_ensemble                      several models' logits rows folded into one     not in the reference
  *
  * Conventions (all functions):
  *   - Return 0 on success or a negative FPNMT_E* code; never throw across the ABI.
@@ -1064,6 +1065,46 @@ int fpnmt_logits_constrain(int rows, int vocab, float* logits, long long ldl, co
                            const int32_t* fin /* may be NULL */, int no_repeat_ngram, float repetition_penalty,
                            int min_len, int end_token, const int32_t* banned /* may be NULL */, int n_banned,
                            fpnmt_stream_t stream);
+
+/* Ensemble decoding (not in the reference; csrc/ensemble.hip): folds the fp32
+ * logits rows of n_models models into one fp32 row per decode row, in one
+ * launch, before fpnmt_logits_constrain and the step kernels, which normalise
+ * the row they are given themselves. logits, ldl and weight are HOST arrays
+ * of n_models entries (logits[m] a device pointer to model m's (rows, vocab)
+ * logits with leading dimension ldl[m]); they are copied into the launch
+ * arguments, so a captured graph holds them and no device-side table has to
+ * stay alive. The weights are used as given: the caller normalises them to
+ * sum 1 (in fp64, before rounding to fp32); nothing is renormalised here.
+ * A row r with fin != NULL and fin[r] != 0 is neither read nor written. For
+ * every other row, with l_m = logits[m] + r*ldl[m], lse_m = logsumexp of
+ * l_m[0 .. vocab) and w_m = weight[m], out[r*ldo + j], 0 <= j < vocab, is
+ *   mode 0 "prob"     log(sum_m w_m * softmax(l_m)[j]), the arithmetic mean of
+ *                     the models' distributions, computed as logsumexp_m(
+ *                     l_m[j] + log w_m - lse_m) and never as a sum of exp of
+ *                     raw logits: a normalised row (its logsumexp is 0);
+ *   mode 1 "logprob"  sum_m w_m * (l_m[j] - lse_m), the geometric mean
+ *                     (log-linear interpolation), left unnormalised: the step
+ *                     kernels renormalise, as they do for constrained rows.
+ * A -inf logit is a token its model gives probability 0: mode 0 leaves that
+ * model out of the column (-inf only where every model has -inf), mode 1
+ * gives -inf where any model has it; such a column is exactly -inf, never a
+ * NaN from inf - inf or 0 * inf. A bad row, in which a model's row holds a
+ * NaN or +inf or is -inf in all columns, has every output column NaN (what
+ * fpnmt_sample_step defines as a row with no drawable token); nothing faults.
+ * Columns vocab .. ldo-1 of out are never written and nothing is read past
+ * column vocab-1 of an input row (ldl[m] may equal vocab). out may be
+ * logits[0] itself (same pointer, ldo == ldl[0]); it may overlap no other
+ * input and logits[0] in no other way. n_models == 1 gives l - lse at weight
+ * 1 in both modes.
+ * FPNMT_E_ARG: a null pointer (the arrays, an entry of logits, out), rows <=
+ * 0, vocab <= 0, n_models < 1, an ldl[m] or ldo < vocab, a weight not finite
+ * or <= 0, mode not 0 or 1, an out that overlaps an input other than as
+ * above. FPNMT_E_UNSUPPORTED: n_models > FPNMT_ENSEMBLE_MAX.                */
+#define FPNMT_ENSEMBLE_MAX 8
+int fpnmt_logits_ensemble(int rows, int vocab, int n_models, const float* const* logits /* host array */,
+                          const long long* ldl /* host array */, const float* weight /* host array */,
+                          int mode /* 0 "prob", 1 "logprob" */, const int32_t* fin /* may be NULL */, float* out,
+                          long long ldo, fpnmt_stream_t stream);
 
 /* Device-side CIDEr-D reward (not in the reference; csrc/cider.hip): the
  * arithmetic of utils/cider_reward.py CiderDReward (n = 4, clipped counts,
