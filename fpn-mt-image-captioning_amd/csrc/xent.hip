@@ -29,60 +29,9 @@
 namespace fpnmt {
 namespace {
 
-constexpr int XS_THREADS = 256;
+// XS_THREADS, XsRed, xs_block_max / _sum / _min, xs_store4, xs_zero_row: common.h
 constexpr int XS_REG_CAP = 10 * 4 * XS_THREADS;  // 10 240 columns
 constexpr int XS_NONE = 0x7fffffff;
-
-struct XsRed {
-  float f[4];
-  int i[4];
-};
-
-__device__ __forceinline__ float xs_block_max(float m, XsRed& red) {
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) red.f[threadIdx.x >> 6] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(red.f[0], red.f[1]), fmaxf(red.f[2], red.f[3]));
-  __syncthreads();
-  return m;
-}
-__device__ __forceinline__ float xs_block_sum(float s, XsRed& red) {
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red.f[threadIdx.x >> 6] = s;
-  __syncthreads();
-  s = red.f[0] + red.f[1] + red.f[2] + red.f[3];
-  __syncthreads();
-  return s;
-}
-__device__ __forceinline__ int xs_block_min(int a, XsRed& red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) a = min(a, __shfl_xor(a, o, 64));
-  if ((threadIdx.x & 63) == 0) red.i[threadIdx.x >> 6] = a;
-  __syncthreads();
-  a = min(min(red.i[0], red.i[1]), min(red.i[2], red.i[3]));
-  __syncthreads();
-  return a;
-}
-
-__device__ __forceinline__ void xs_store4(float* p, float a, float b, float c, float d) {
-  *reinterpret_cast<float4*>(p) = make_float4(a, b, c, d);
-}
-__device__ __forceinline__ void xs_store4(bf16* p, float a, float b, float c, float d) {
-  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-  bf16x4 o = {(bf16)a, (bf16)b, (bf16)c, (bf16)d};
-  *reinterpret_cast<bf16x4*>(p) = o;
-}
-
-template <typename T, bool VEC>
-__device__ __forceinline__ void xs_zero_row(T* dr, int v) {
-  if (VEC) {
-    const int nv = v >> 2;
-    for (int k = threadIdx.x; k < nv; k += XS_THREADS) xs_store4(dr + 4 * k, 0.f, 0.f, 0.f, 0.f);
-    for (int j = (nv << 2) + threadIdx.x; j < v; j += XS_THREADS) dr[j] = from_f32<T>(0.f);
-  } else {
-    for (int j = threadIdx.x; j < v; j += XS_THREADS) dr[j] = from_f32<T>(0.f);
-  }
-}
 
 // the smoothed target: a on the label, b everywhere
 struct XsTarget {

@@ -149,6 +149,10 @@ class GuardDesc(C.Structure):
     _fields_ = [("global_clipnorm", C.c_float), ("reserved", C.c_int32 * 3)]
 
 
+class DistillDesc(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("temperature", C.c_float), ("reserved", C.c_float * 2)]
+
+
 class GuardState(C.Structure):
     _fields_ = [("sumsq_total", C.c_float), ("clip_factor", C.c_float), ("skipped", C.c_int32),
                 ("consecutive", C.c_int32), ("n_skipped", C.c_longlong), ("n_applied", C.c_longlong)]
@@ -228,6 +232,7 @@ SIGNATURES = {
     "fpnmt_xent_weighted_fwd_bwd": [I, LL, I, P, LL, P, P, I, P, P, P, LL, F, P],
     "fpnmt_repeat_rows": [I, I, I, LL, P, P, P],
     "fpnmt_xent_smooth_fwd_bwd": [I, LL, I, P, LL, P, F, P, P, P, P, LL, F, P],
+    "fpnmt_xent_distill_fwd_bwd": [I, LL, I, P, LL, P, LL, P, F, P, P, P, P, LL, F, P],
     "fpnmt_caption_stats": [LL, I, P, P, P, P, P, P, P, I, P],
     "fpnmt_grad_sumsq": [I, P, P, I, P, P, P, F, P, P],
     "fpnmt_amsgrad_step": [C.POINTER(AdamDesc), I, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P],

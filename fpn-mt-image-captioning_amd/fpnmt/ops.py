@@ -2219,6 +2219,49 @@ class SmoothedXentFn(torch.autograd.Function):
         return dlog.reshape(ctx.shape), None, None
 
 
+class DistillXentFn(torch.autograd.Function):
+    """SmoothedXentFn mixed with the KL divergence from a dense teacher row
+    (fpnmt_xent_distill_fwd_bwd): (1 - alpha) * smoothed CE + alpha * T^2 *
+    KL(softmax(teacher / T) || softmax(logits / T)), a mean over ALL rows.
+    teacher has the logits' (..., V) shape, fp32; the kernel normalises it,
+    so raw logits and a fold of several models' both do. desc is the 16-byte
+    device record {alpha, T, 0, 0} (fpnmt.distill.DistillDesc.table), read at
+    execution: a replayed graph sees what was written into it since.
+    Returns (loss, stats): the scalar loss[0] and the (3,) tensor {loss, hard
+    CE, KL} (not differentiable). The gradient is computed in the same launch
+    (saved) — the loss must be the root of backward; teacher and desc get no
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, teacher, eps, desc):
+        v = logits.shape[-1]
+        if logits.dtype != torch.float32 or teacher.dtype != torch.float32:
+            raise TypeError("DistillXentFn expects fp32 logits and an fp32 teacher")
+        if tuple(teacher.shape) != tuple(logits.shape):
+            raise ValueError(f"DistillXentFn: teacher {tuple(teacher.shape)} for logits {tuple(logits.shape)}")
+        if desc.dtype != torch.float32 or desc.numel() != 4 or not desc.is_contiguous() or desc.device != logits.device:
+            raise TypeError("DistillXentFn: desc must be the contiguous (4,) fp32 device record")
+        lg = logits.reshape(-1, v).contiguous()
+        te = teacher.reshape(-1, v).contiguous()
+        lab = labels.reshape(-1).to(torch.int32).contiguous()
+        rows = lg.shape[0]
+        stats = torch.empty((3,), dtype=torch.float32, device=lg.device)
+        need = ctx.needs_input_grad[0]
+        dlog = torch.empty_like(lg) if need else None
+        call("fpnmt_xent_distill_fwd_bwd", L.F32, rows, v, ptr(lg), v, ptr(te), v, ptr(lab), float(eps), ptr(desc),
+             ptr(stats), None, ptr(dlog), v, 1.0, stream_ptr())
+        if need:
+            ctx.save_for_backward(dlog)
+        ctx.shape = logits.shape
+        ctx.mark_non_differentiable(stats)
+        return stats[0].clone(), stats  # a tensor of its own: an output must not be a view of another
+
+    @staticmethod
+    def backward(ctx, g, _):
+        (dlog,) = ctx.saved_tensors
+        return dlog.reshape(ctx.shape), None, None, None, None
+
+
 def caption_eval(logits, labels, eps, totals, accumulate):
     """The held-out statistics of teacher-forced logits (captions, t, V) fp32
     against labels (captions, t): the smoothed loss in the step's convention

@@ -22,6 +22,13 @@ weights[r] (ops.WeightedXentFn, still a mean over all rows). Its graphs are
 captured per shape beside the plain step's; arena, optimizer state and step
 counter are shared, so the two kinds of step can alternate.
 
+step_distill(img, tok, teacher_logits=None) is step() with the loss swapped
+for token-level knowledge distillation (not in the reference; set_distill,
+fpnmt/distill.py): the teachers run teacher-forced in inference mode ahead
+of the student's forward, in the same graph, and the loss is
+ops.DistillXentFn. Its graphs are kept beside the others and share the same
+arena, optimizer kernel, guard, average and parameter groups.
+
 With world > 1 (or split_backward=True) the step is a sequence of graphs:
   G1      forward + loss + the decoder's backward (stops at the encoder
           output, which enters the decoder as a leaf)
@@ -51,6 +58,7 @@ import torch.distributed as dist
 import fpnmt
 from . import _lib as L
 from . import dist as fdist
+from . import distill as fdistill
 from . import layers as flayers
 from . import ops
 from .arena import ParamArena, check_ema_decay, check_global_clipnorm
@@ -229,6 +237,9 @@ class TrainEngine:
         self.static = None
         self._wsteps = {}  # step_weighted: shapes -> [calls, graphs, static]
         self._esteps = {}  # eval_step: shapes -> [calls, graph, static inputs, outputs]
+        self._distill = None  # set_distill: the teachers, the fold and the device descriptor
+        self._dsteps = {}  # step_distill: shapes -> [calls, graphs, static]
+        self._distill_stats = None
         self._eval_gen = -1  # the compute copies' generation the eval graphs last saw
         self.eval_totals = torch.zeros(3, dtype=torch.float64, device=dev)  # eval_step(accumulate=True)
 
@@ -322,10 +333,10 @@ class TrainEngine:
         """Freeze (flag True) or unfreeze group `name`: flips requires_grad on
         its parameters, so the backward no longer visits them (pruned, not
         masked), and the frozen flag of their segments in the device table.
-        The captured step graphs (step, step_weighted, the split sequence) are
-        dropped, since the autograd graph they recorded changed: the next
-        call at a shape runs eagerly and the one after captures, as at
-        start-up. Eval graphs are kept. Optimizer state is kept too: a frozen
+        The captured step graphs (step, step_weighted, step_distill, the split
+        sequence) are dropped, since the autograd graph they recorded changed:
+        the next call at a shape runs eagerly and the one after captures, as
+        at start-up. Eval graphs are kept. Optimizer state is kept too: a frozen
         group's m, v and vhat stay as they are, and after unfreezing it
         continues from them with the global step counter (its bias correction
         is that of the current step, not of the steps it took part in)."""
@@ -343,6 +354,8 @@ class TrainEngine:
         self.graphs = None
         self.static = None
         self._wsteps = {}
+        self._dsteps = {}
+        self._distill_stats = None
         flayers.invalidate_weights()  # an unfrozen layer comes back into the refresh
 
     # ----------------------------------------------------- weight averaging
@@ -480,13 +493,23 @@ class TrainEngine:
         if zs is not None:
             torch.cuda.current_stream().wait_stream(zs)
 
-    def _logits_loss(self, enc_fn, tok, weights):
+    def _logits_loss(self, enc_fn, tok, weights, soft=None):
         """targets -> encoder output (enc_fn) -> decoder -> logits -> loss.
         weights None: the plain step's masked CE. Otherwise tok holds
         n = rows / images captions per image: the encoder output is repeated n
-        times and caption r's terms are weighted by weights[r]."""
+        times and caption r's terms are weighted by weights[r].
+        soft (step_distill): ("run", img) runs the teachers on img ahead of
+        the student's forward, ("given", logits) takes precomputed soft
+        targets; the loss is then ops.DistillXentFn."""
         m = self.model
         tar_inp, tar_real, mask = ops.decoder_targets(tok)  # tok[:, :-1], tok[:, 1:], create_masks(tar_inp)
+        if soft is not None:
+            d = self._distill
+            tea = d.teacher_logits(soft[1], tar_inp, mask) if soft[0] == "run" else soft[1]
+            dec, _ = m.decoder(tar_inp, enc_fn(), True, mask, None)
+            loss, self._distill_stats = ops.DistillXentFn.apply(m.final_layer(dec), tar_real, tea,
+                                                                self.label_smoothing, d.desc.table)
+            return loss
         enc = enc_fn()
         if weights is None:
             dec, _ = m.decoder(tar_inp, enc, True, mask, None)
@@ -496,7 +519,7 @@ class TrainEngine:
         dec, _ = m.decoder(tar_inp, ops.RepeatRowsFn.apply(enc, tok.shape[0] // enc.shape[0]), True, mask, None)
         return ops.WeightedXentFn.apply(m.final_layer(dec), tar_real, weights, tok.shape[1] - 1)
 
-    def _fwd_bwd(self, img, tok, weights=None):
+    def _fwd_bwd(self, img, tok, weights=None, soft=None):
         ops.runtime.reset_sites()  # dropout sites numbered from the step's start
         ops.reset_grad_sums()
         zs = self._zero_grad_fork()
@@ -506,7 +529,7 @@ class TrainEngine:
                  and 0 < self.early_blocks < self.arena.nblocks)
         ops.runtime.on_transformer_grads = self._early_update if early else None
         try:
-            loss = self._logits_loss(lambda: self.model.encoder(img, True, None), tok, weights)
+            loss = self._logits_loss(lambda: self.model.encoder(img, True, None), tok, weights, soft)
             self._zero_grad_join(zs)
             with L.deferred_reductions(fpnmt.config.defer_reductions), ops.side_wgrad():
                 torch.autograd.backward([loss], [self._one(loss)])  # ordered reductions batched at the exit
@@ -540,7 +563,7 @@ class TrainEngine:
                                     ema=self.arena.ema is not None, **self.adam)
         self._early_pending = True
 
-    def _fwd_bwd_split(self, img, tok, weights=None):
+    def _fwd_bwd_split(self, img, tok, weights=None, soft=None):
         """G1: forward + loss + the decoder's backward down to the encoder
         output (a leaf of the decoder; with weights, the leaf is the encoder
         output per image, ahead of its repeat)."""
@@ -556,7 +579,7 @@ class TrainEngine:
             enc = m.encoder.from_features(leaves, True, None)
             side.update(stages=stages, leaves=leaves, enc=enc, enc_leaf=enc.detach().requires_grad_(True))
             return side["enc_leaf"]
-        loss = self._logits_loss(encode, tok, weights)
+        loss = self._logits_loss(encode, tok, weights, soft)
         stages, leaves, enc, enc_leaf = side["stages"], side["leaves"], side["enc"], side["enc_leaf"]
         self._zero_grad_join(zs)
         with L.deferred_reductions(fpnmt.config.defer_reductions), ops.side_wgrad():
@@ -639,9 +662,9 @@ class TrainEngine:
         if fp:
             fp.mark_fresh()
 
-    def _eager(self, img, tok, weights=None):
+    def _eager(self, img, tok, weights=None, soft=None):
         if self.split:
-            loss = self._fwd_bwd_split(img, tok, weights)
+            loss = self._fwd_bwd_split(img, tok, weights, soft)
             works = self._exchange(0, wait=False)
             self._bwd_encoder()
             works += self._exchange(1, wait=False)
@@ -653,7 +676,7 @@ class TrainEngine:
             for w in works:
                 w.wait()
         else:
-            loss = self._fwd_bwd(img, tok, weights)
+            loss = self._fwd_bwd(img, tok, weights, soft)
             self._exchange()
         self._update()
         return loss.detach()
@@ -730,6 +753,117 @@ class TrainEngine:
         static[1].copy_(tok)
         static[3].copy_(weights)
         return self._replay(graphs, static[2])
+
+    # ------------------------------------------------------- distillation
+    def set_distill(self, teachers, alpha=0.5, temperature=1.0, ensemble_mode="prob", ensemble_weights=None):
+        """Turn token-level knowledge distillation on for step_distill (not in
+        the reference). teachers: a sequence of Transformers with the
+        student's vocabulary on its device, at most fpnmt._lib.ENSEMBLE_MAX;
+        they may differ in depth, width and backbone. It may be empty when
+        every step_distill call brings teacher_logits. Several teachers are
+        folded as the decode-time ensemble is (fpnmt_logits_ensemble,
+        ensemble_mode "prob" or "logprob", ensemble_weights one per teacher,
+        normalised; the student is not part of the mix). The loss is
+        (1 - alpha) * CE at the engine's label_smoothing + alpha *
+        temperature^2 * KL(teacher || student) at that temperature; alpha in
+        [0, 1], temperature finite > 0. Both live in a 16-byte device record
+        allocated here, which set_distill_alpha / set_distill_temperature
+        write in place. The engine holds the teachers strongly and never
+        writes to them; their compute copies are refreshed outside the graph
+        before a step when layers.invalidate_weights() made them stale (new
+        weights loaded into a teacher). The positional-table length cannot be
+        checked here, where no caption length is known: step_distill checks
+        it against its tokens when it runs the teachers (with teacher_logits=
+        the teachers are not run and nothing needs the table).
+        set_distill(None) clears them and drops the
+        distillation graphs; step, step_weighted and eval_step launch what
+        they launched before either way."""
+        self._dsteps = {}
+        self._distill_stats = None
+        if teachers is None:
+            self._distill = None
+            return
+        self._distill = fdistill.Distill(self.model, teachers, alpha, temperature, ensemble_mode, ensemble_weights)
+
+    def _require_distill(self, who):
+        if self._distill is None:
+            raise ValueError(f"TrainEngine.{who}: call set_distill first")
+        return self._distill
+
+    def set_distill_alpha(self, alpha):
+        """A new alpha from the next step on, written into the device record
+        in place (stream-ordered): captured steps are kept and the next
+        replay reads the new value, like set_ema_decay."""
+        self._require_distill("set_distill_alpha").desc.set_alpha(alpha)
+
+    def set_distill_temperature(self, temperature):
+        """A new temperature from the next step on; in place, no recapture."""
+        self._require_distill("set_distill_temperature").desc.set_temperature(temperature)
+
+    @property
+    def distill_stats(self):
+        """The last step_distill's (3,) fp32 device tensor {loss, hard CE
+        (without the 1 - alpha), KL (without the alpha T^2)}, means over all
+        rows; no synchronisation. None before the first such step. After a
+        replayed step it is the graph's static tensor, overwritten by the
+        next replay."""
+        return self._distill_stats
+
+    def step_distill(self, img, tok, teacher_logits=None):
+        """One distillation step: step() with the loss swapped for
+        ops.DistillXentFn against the teachers' soft targets. Each teacher
+        runs teacher-forced on (img, tok[:, :-1]) in inference mode under
+        no_grad, ahead of the student's forward on the compute stream (it
+        writes nothing and advances no dropout counter); teacher_logits
+        (B, T_full - 1, V) fp32 on the device replaces that pass with
+        precomputed soft targets (raw logits or log-probabilities: the kernel
+        normalises). Returns the (device) loss; distill_stats holds its
+        parts. Per input shape the first call runs eagerly, the second
+        captures, later ones copy image, tokens (and teacher_logits) into
+        static buffers and replay. Arena, optimizer kernel, guard, average
+        and parameter groups are step()'s, so the kinds of step can
+        alternate. A NaN in the soft targets makes the loss and the gradient
+        NaN: the step guard, when on, skips such a step."""
+        d = self._require_distill("step_distill")
+        B = img.shape[0]
+        if tok.dim() != 2 or tok.shape[0] != B or tok.shape[1] < 2:
+            raise ValueError(f"step_distill: {tuple(tok.shape)} captions for {B} images")
+        if teacher_logits is None:
+            if not d.teachers:
+                raise ValueError("step_distill: set_distill was given no teachers; pass teacher_logits")
+            d.check_len(tok.shape[1] - 1)
+        else:
+            want = (B, tok.shape[1] - 1, d.vocab)
+            if (not torch.is_tensor(teacher_logits) or tuple(teacher_logits.shape) != want
+                    or teacher_logits.dtype != torch.float32 or teacher_logits.device != d.device):
+                got = ((teacher_logits.dtype, tuple(teacher_logits.shape), str(teacher_logits.device))
+                       if torch.is_tensor(teacher_logits) else type(teacher_logits))
+                raise ValueError(f"step_distill: teacher_logits must be fp32 of shape {want} on {d.device}, got {got}")
+        self._check_trainable_now("step_distill")
+        given = teacher_logits is not None
+        key = (tuple(img.shape), tuple(tok.shape), tok.dtype, given)
+        ent = self._dsteps.setdefault(key, [0, None, None])
+        ent[0] += 1
+        if not self.use_graph or ent[0] == 1:
+            dt = fpnmt.compute_dtype()
+            flayers.prepare_all(self.model, dt)
+            if not given:
+                for t in d.teachers:
+                    flayers.prepare_all(t, dt)
+            return self._eager(img, tok, None, ("given", teacher_logits) if given else ("run", img))
+        self._refresh_frozen_copies()
+        if not given:
+            d.refresh_copies(fpnmt.compute_dtype())
+        if ent[1] is None:
+            ent[1], ent[2] = self._capture(img, tok, None, teacher_logits if given else "run")
+        graphs, static = ent[1], ent[2]
+        static[0].copy_(img)
+        static[1].copy_(tok)
+        if given:
+            static[4].copy_(teacher_logits)
+        loss = self._replay(graphs, static[2])
+        self._distill_stats = static[5]
+        return loss
 
     # ---------------------------------------------------------- held out
     def reset_eval_totals(self):
@@ -838,17 +972,24 @@ class TrainEngine:
             g_up.replay()
         return loss
 
-    def _capture(self, img, tok, weights=None):
+    def _capture(self, img, tok, weights=None, soft=None):
         """Capture the step on static copies of its inputs. The plain step's
         graphs become self.graphs / self.static; a weighted step's (graphs,
-        static) are returned to step_weighted."""
+        static) are returned to step_weighted, a distillation step's (soft:
+        "run", or the teacher logits to make a static copy of) to
+        step_distill, with the static soft targets and the step's (3,)
+        statistics as static[4] and static[5]."""
         s_img = img.detach().clone()
         s_tok = tok.detach().clone()
         s_w = weights.detach().clone() if weights is not None else None
+        s_z = None
+        if soft is not None:
+            s_z = soft.detach().clone() if torch.is_tensor(soft) else None
+            soft = ("given", s_z) if s_z is not None else ("run", s_img)
         out = {}
         if self.split:
             def g1():
-                out["loss"] = self._fwd_bwd_split(s_img, s_tok, s_w).detach()
+                out["loss"] = self._fwd_bwd_split(s_img, s_tok, s_w, soft).detach()
             n = len(self.model.encoder.feature_extractor.stage_prefixes())
             live = [i for i in range(n) if not self._range_frozen(2 + i)]
             stage_fns = [(lambda i=i: self._bwd_stage(i)) for i in live]
@@ -859,14 +1000,16 @@ class TrainEngine:
             graphs = got[:2] + stage_graphs + got[-1:]
         elif self.world == 1:
             def g():
-                out["loss"] = self._fwd_bwd(s_img, s_tok, s_w).detach()
+                out["loss"] = self._fwd_bwd(s_img, s_tok, s_w, soft).detach()
                 self._update()
             graphs = (capture_sequence([g])[0], None)
         else:
             def g1():
-                out["loss"] = self._fwd_bwd(s_img, s_tok, s_w).detach()
+                out["loss"] = self._fwd_bwd(s_img, s_tok, s_w, soft).detach()
             graphs = tuple(capture_sequence([g1, self._update]))
         static = (s_img, s_tok, out["loss"], s_w)
+        if soft is not None:
+            return graphs, static + (s_z, self._distill_stats)
         if weights is None:
             self.graphs, self.static = graphs, static
         return graphs, static

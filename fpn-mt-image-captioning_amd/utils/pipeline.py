@@ -226,6 +226,51 @@ class Pipeline:
         return tr.step(img, refs, n_samples=n_samples, baseline=baseline, reward=reward, temperature=temperature,
                        top_k=top_k, top_p=top_p, seed=seed, image_keys=image_keys)
 
+    # ------------------------------------------------------- distillation
+    def set_teachers(self, teachers, alpha=0.5, temperature=1.0, ensemble_mode="prob", ensemble_weights=None):
+        """Token-level knowledge distillation (not in the reference): put what
+        an ensemble, a larger model or an averaged checkpoint knows into this
+        model, which then decodes at single-model cost. teachers: Transformers
+        (load_member's results) or Pipelines (their .transformer), with this
+        vocabulary on this device, at most fpnmt._lib.ENSEMBLE_MAX; several
+        are folded as predict_batch(ensemble=...) folds them (ensemble_mode,
+        ensemble_weights one per teacher). train_step_distill then trains on
+        (1 - alpha) * the train_step loss + alpha * temperature^2 * KL(teachers
+        || model) at that temperature (TrainEngine.set_distill);
+        engine.set_distill_alpha / set_distill_temperature anneal either
+        between steps. set_teachers(None) turns it off. Checkpoints carry
+        neither the teachers nor alpha / temperature: the teachers are
+        external models, and a restored pipeline calls set_teachers again."""
+        if teachers is not None:
+            teachers = [t.transformer if isinstance(t, Pipeline) else t for t in teachers]
+        self.engine.set_distill(teachers, alpha, temperature, ensemble_mode, ensemble_weights)
+
+    def train_step_distill(self, img, caption_token, teacher_logits=None):
+        """train_step against the teachers' soft targets
+        (TrainEngine.step_distill): one optimizer step, then
+        train_loss(loss) with the mixed loss, a skipped step left out under
+        the step guard as in train_step. teacher_logits (B, T - 1, V) fp32 on
+        the device: precomputed soft targets instead of running the
+        teachers."""
+        loss = self.engine.step_distill(img, caption_token, teacher_logits)
+        if self.engine.guard_on:
+            self.train_loss(loss, keep=1 - self.engine.step_skipped)
+        else:
+            self.train_loss(loss)
+        return loss
+
+    def distill_stats(self):
+        """The last train_step_distill's parts, one read-back: {"loss" (the
+        mixed loss), "hard" (the smoothed CE, without the 1 - alpha), "kl"
+        (without the alpha T^2)}, means over all positions; with "alpha" and
+        "temperature" as set."""
+        s = self.engine.distill_stats
+        if s is None:
+            raise ValueError("Pipeline.distill_stats: no train_step_distill has run")
+        loss, hard, kl = s.tolist()
+        d = self.engine._distill
+        return {"loss": loss, "hard": hard, "kl": kl, "alpha": d.desc.alpha, "temperature": d.desc.temperature}
+
     # ----------------------------------------------------------- held out
     def eval_step(self, img, caption_token, weights="model"):
         """The loss of one held-out batch without an optimizer step (not in the

@@ -25,6 +25,7 @@
  *   fpnmt_logits_constrain                     n-gram blocking, repetition penalty, min length  not in the reference
  *   fpnmt_ciderd_reward, fpnmt_scst_pack       CIDEr-D reward and advantages on the device     not in the reference
  *   fpnmt_logits_ensemble                      several models' logits rows folded into one     not in the reference
+ *   fpnmt_xent_distill_fwd_bwd                 smoothed CE mixed with KL to teachers' rows     not in the reference
  *
  * Conventions (all functions):
  *   - Return 0 on success or a negative FPNMT_E* code; never throw across the ABI.
@@ -686,6 +687,50 @@ int fpnmt_repeat_rows(int dtype, int b, int n, long long len, const void* x, voi
 int fpnmt_xent_smooth_fwd_bwd(int dtype, long long rows, int v, const float* logits, long long ld,
                               const int32_t* labels, float eps, float* loss, float* row_logp, int32_t* row_hit,
                               void* dlogits, long long ldd, float dloss_scale, fpnmt_stream_t stream);
+
+/* ---- token-level knowledge distillation: CE mixed with KL to a teacher row --
+ * The label-smoothed masked CE above mixed with the KL divergence from a
+ * dense teacher row at temperature T (Hinton et al. 2015; word-level
+ * distillation, Kim & Rush 2016). teacher holds fp32 logits in the sense that
+ * the kernel normalises them: raw logits, log-probabilities or the fold
+ * fpnmt_logits_ensemble writes all do. With a = desc->alpha, T =
+ * desc->temperature, mask_r = label_r in (0, v), p = softmax(x), pT =
+ * softmax(x / T), q = softmax(t / T) per row:
+ *   ce_r         = lse(x) - (1 - eps) x_lab - (eps / v) sum_j x_j   (as fpnmt_xent_smooth_fwd_bwd)
+ *   kl_r         = sum_j q_j (log q_j - log pT_j)
+ *   loss[0]      = (1 / rows) sum_r mask_r ((1 - a) ce_r + a T^2 kl_r)
+ *   loss[1]      = (1 / rows) sum_r mask_r ce_r        (without the 1 - a)
+ *   loss[2]      = (1 / rows) sum_r mask_r kl_r        (without the a T^2)
+ *                  (means over ALL rows; each summed in row order by one block
+ *                  through the workspace: bitwise repeatable),
+ *   dlogits[r,j] = dloss_scale * mask_r / rows * ((1 - a) (p_j - (1 - eps) [j == label_r] - eps / v)
+ *                                                 + a T (pT_j - q_j))
+ *                  (dtype bf16 or fp32; may be NULL; exact zeros on a pad row
+ *                  and for dloss_scale == 0),
+ *   row_logp[r]  = x_lab - lse(x), 0 on a pad (may be NULL).
+ * desc is DEVICE memory, read by the kernel at execution: a captured step
+ * changes alpha or T by writing the 16 bytes, without recapture. The entry
+ * point cannot validate them (callers keep alpha in [0, 1], T finite > 0).
+ * A pad row reads neither logits nor teacher. A -inf teacher entry is a token
+ * of probability zero: it adds exactly 0 to kl_r and its gradient is
+ * a T pT_j. A teacher row with a NaN or +inf, or -inf throughout, makes kl_r,
+ * loss[0] and loss[2] NaN (and that row's gradient); nothing faults and the
+ * other rows' gradients are unaffected. Both rows are read once and held in
+ * registers up to v = 10 240; wider rows take an online pass and a second
+ * read. Nothing is touched past column v - 1 of a row.
+ * rows == 0 zeroes loss[0..2]. No allocation, no synchronisation, capturable.
+ * FPNMT_E_ARG: null logits / teacher / labels / desc / loss, eps outside
+ * [0, 1) or NaN, a bad dtype, v < 1, ld < v, ldt < v, ldd < v with a gradient,
+ * rows outside [0, 2^31), no workspace attached.                            */
+typedef struct fpnmt_distill_desc {
+  float alpha;       /* weight of the KL term, in [0, 1] */
+  float temperature; /* T, finite and > 0 */
+  float reserved[2]; /* 0 */
+} fpnmt_distill_desc;
+int fpnmt_xent_distill_fwd_bwd(int dtype, long long rows, int v, const float* logits, long long ld,
+                               const float* teacher, long long ldt, const int32_t* labels, float eps,
+                               const fpnmt_distill_desc* desc /* device */, float* loss /* [3] */, float* row_logp,
+                               void* dlogits, long long ldd, float dloss_scale, fpnmt_stream_t stream);
 
 /* ---- per-caption and total statistics of a teacher-forced batch -----------
  * Rows are captions * t, caption-major; a position is live when its label is
