@@ -678,6 +678,311 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_log_kernel(
   if (__syncthreads_and(fin) && tid == 0) status[img] = 1;
 }
 
+// ---- diverse beam step (BeamDecoder mode="beam", beam_groups > 1) ----------
+// The sibling of beam_step_log_kernel for diverse beam search (Vijayakumar et
+// al.): the image's K rows are G groups of Kg = K / G contiguous rows, ranked
+// one group after the other. A live row's candidate for token j is
+// (logit[j] + coff) - lam * cnt[j], cnt[j] the number of live children of the
+// EARLIER groups that took j at this position; only the group's own rows
+// compete for its Kg slots. Finished rows carry themselves unpenalised and
+// uncounted, and the score a child carries is the unpenalised logit + coff,
+// recomputed from the logit when the tables are written, so the scores stay
+// sums of log-probabilities. Everything else (statistics pass, better(), the
+// selection rounds, the table writes, the frozen image, the empty slot) is
+// beam_step_log_kernel's, kept as a copy so that kernel stays what it is.
+//  * cnt lives in LDS as at most K - Kg distinct tokens with counts; in front
+//    of it a 2048-bit filter on token & 2047. The four tokens of a 16-B load
+//    share one filter word (4 j is 4-aligned), so a load whose nibble is 0,
+//    the common one, costs one LDS word; only a hit walks the list.
+//  * a group's candidate pass strides the whole block over its rows (8 waves
+//    on Kg rows, not a wave per row: Kg may be 1). Any partition of the
+//    candidates gives the same top Kg.
+//  * L >= Kg is the per-thread list length (1, 2, 4, 8 or 16): a short group
+//    keeps a short list in registers and LDS.
+constexpr int DIV_FILTER_BITS = 2048;
+
+// fp32 product, then the subtraction: never one FMA with the add before it
+__device__ __forceinline__ float diversity_penalised(float v, float lam, int cnt) {
+#pragma clang fp contract(off)
+  const float pen = lam * (float)cnt;
+  return v - pen;
+}
+
+template <int L>
+__global__ __launch_bounds__(BS_THREADS) void beam_step_groups_kernel(
+    int beam_n, int groups, float lam, int vocab, const float* __restrict__ logits, long long ldl,
+    float* __restrict__ beam_score, int32_t* __restrict__ beam_len, int32_t* __restrict__ beam_fin,
+    const int32_t* __restrict__ hist_in, int32_t* __restrict__ hist_out, int hist_ld, int t,
+    const int32_t* __restrict__ src_in, int32_t* __restrict__ src_out, int src_ld, int end_token,
+    int32_t* __restrict__ tok_out, int32_t* __restrict__ status) {
+  const int img = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int NW = BS_THREADS / 64;
+  constexpr int NONE = 0x7fffffff;
+  __shared__ float coff[BEAM_MAX], bscore[BEAM_MAX];
+  __shared__ int blen[BEAM_MAX], bfin[BEAM_MAX], live[BEAM_MAX];
+  __shared__ float lv[BS_THREADS][L];
+  __shared__ int li[BS_THREADS][L];
+  __shared__ float sel_v[BEAM_MAX];
+  __shared__ int sel_i[BEAM_MAX];
+  __shared__ float red_v[NW];
+  __shared__ int red_i[NW], red_t[NW];
+  __shared__ unsigned filt[DIV_FILTER_BITS / 32];
+  __shared__ int pen_tok[BEAM_MAX], pen_cnt[BEAM_MAX], pen_n;
+  const int row0 = img * beam_n;
+  const int K = beam_n, Kg = beam_n / groups;
+  if (status[img] != 0) {  // block-uniform: frozen image
+    for (int e = tid; e < K * (t + 2); e += BS_THREADS) {
+      const int k = e / (t + 2), pos = e - k * (t + 2);
+      const int r = row0 + k;
+      hist_out[(long long)r * hist_ld + pos] = pos <= t ? hist_in[(long long)r * hist_ld + pos] : end_token;
+      if (pos <= t) src_out[(long long)r * src_ld + pos] = src_in[(long long)r * src_ld + pos];
+      else if (pos < src_ld) src_out[(long long)r * src_ld + pos] = r;
+    }
+    return;
+  }
+  if (tid < K) {
+    const float s = beam_score[row0 + tid];
+    const int f = beam_fin[row0 + tid] != 0;
+    bscore[tid] = s;
+    blen[tid] = beam_len[row0 + tid];
+    bfin[tid] = f;
+    live[tid] = !f && s > -INFINITY;  // false for NaN too
+  }
+  if (tid < DIV_FILTER_BITS / 32) filt[tid] = 0u;
+  if (tid == 0) pen_n = 0;
+  __syncthreads();
+  const bool vec = (vocab & 3) == 0 && (ldl & 3) == 0 && ((uintptr_t)logits & 15) == 0;
+  const int nv4 = vocab >> 2;
+  // 1. per live beam: score - logsumexp(logits row) (wave per beam row), once
+  //    for all groups
+  for (int b = wave; b < beam_n; b += NW) {
+    if (!live[b]) continue;  // wave-uniform
+    const float* lr = logits + (long long)(row0 + b) * ldl;
+    float mx = -INFINITY;
+    if (vec) {
+      const f32x4* l4 = (const f32x4*)lr;
+      int j = lane;
+      for (; j + 192 < nv4; j += 256) {
+        const f32x4 a = l4[j], c = l4[j + 64], d = l4[j + 128], e = l4[j + 192];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mx = fmaxf(mx, fmaxf(fmaxf(a[q], c[q]), fmaxf(d[q], e[q])));
+      }
+      for (; j < nv4; j += 64) {
+        const f32x4 a = l4[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) mx = fmaxf(mx, a[q]);
+      }
+    } else {
+      for (int j = lane; j < vocab; j += 64) mx = fmaxf(mx, lr[j]);
+    }
+    mx = wave_max(mx);
+    float s = 0.f;
+    if (vec) {
+      const f32x4* l4 = (const f32x4*)lr;
+      int j = lane;
+      for (; j + 192 < nv4; j += 256) {
+        const f32x4 a = l4[j], c = l4[j + 64], d = l4[j + 128], e = l4[j + 192];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += expf(a[q] - mx);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += expf(c[q] - mx);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += expf(d[q] - mx);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += expf(e[q] - mx);
+      }
+      for (; j < nv4; j += 64) {
+        const f32x4 a = l4[j];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += expf(a[q] - mx);
+      }
+    } else {
+      for (int j = lane; j < vocab; j += 64) s += expf(lr[j] - mx);
+    }
+    s = wave_sum(s);
+    if (lane == 0) coff[b] = bscore[b] - (mx + logf(s));
+  }
+  __syncthreads();
+  for (int g = 0; g < groups; ++g) {
+    const int b0 = g * Kg;
+    const int np = pen_n;  // written before the barrier that ended the last group
+    const bool pen_on = lam > 0.f && np > 0;
+    // 2. per-thread sorted top-L of the group's candidates (flat index
+    //    f = b * V + j, b the row inside the image)
+    float tv[L];
+    int ti[L];
+#pragma unroll
+    for (int k = 0; k < L; ++k) {
+      tv[k] = -INFINITY;
+      ti[k] = NONE;
+    }
+    auto offer = [&](float c, int f) {
+      if (better(c, f, tv[L - 1], ti[L - 1])) {
+        // compile-time indices only, as in beam_step_kernel
+        float cv = c;
+        int ci = f;
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+          if (better(cv, ci, tv[k], ti[k])) {
+            const float sv = tv[k];
+            const int si = ti[k];
+            tv[k] = cv;
+            ti[k] = ci;
+            cv = sv;
+            ci = si;
+          }
+        }
+      }
+    };
+    // a filter hit: the token's count from the list (0: another token on the same bit)
+    auto hit_value = [&](float v, int j) {
+      int c = 0;
+      for (int p = 0; p < np; ++p)
+        if (pen_tok[p] == j) c = pen_cnt[p];
+      return diversity_penalised(v, lam, c);
+    };
+    if (vec) {
+      for (int b = b0; b < b0 + Kg; ++b) {
+        if (!live[b]) continue;  // block-uniform
+        const f32x4* l4 = (const f32x4*)(logits + (long long)(row0 + b) * ldl);
+        const float co = coff[b];
+        const int f0 = b * vocab;
+        auto four = [&](const f32x4 a, int j4) {  // tokens j4 .. j4 + 3, one filter word
+          const unsigned hit = pen_on ? (filt[(j4 & (DIV_FILTER_BITS - 1)) >> 5] >> (j4 & 31)) & 0xfu : 0u;
+          float v[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) v[q] = a[q] + co;
+          if (hit) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              if ((hit >> q) & 1u) v[q] = hit_value(v[q], j4 + q);
+          }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) offer(v[q], f0 + j4 + q);
+        };
+        int j = tid;
+        for (; j + BS_THREADS < nv4; j += 2 * BS_THREADS) {
+          const f32x4 a = l4[j], c = l4[j + BS_THREADS];
+          four(a, 4 * j);
+          four(c, 4 * (j + BS_THREADS));
+        }
+        for (; j < nv4; j += BS_THREADS) four(l4[j], 4 * j);
+      }
+    } else {
+      const int total = Kg * vocab;
+      for (int f = tid; f < total; f += BS_THREADS) {
+        const int bl = f / vocab, j = f - bl * vocab;
+        const int b = b0 + bl;
+        if (!live[b]) continue;
+        float v = logits[(long long)(row0 + b) * ldl + j] + coff[b];
+        if (pen_on && ((filt[(j & (DIV_FILTER_BITS - 1)) >> 5] >> (j & 31)) & 1u)) v = hit_value(v, j);
+        offer(v, b * vocab + j);
+      }
+    }
+    // a finished beam's single candidate: itself, ending in <end>, unpenalised
+    if (tid < Kg && bfin[b0 + tid]) offer(bscore[b0 + tid], (b0 + tid) * vocab + end_token);
+#pragma unroll
+    for (int k = 0; k < L; ++k) {
+      lv[tid][k] = tv[k];
+      li[tid][k] = ti[k];
+    }
+    __syncthreads();
+    // 3. Kg rounds of a block arg-best over the list heads
+    int head = 0;
+    for (int round = 0; round < Kg; ++round) {
+      float bv = head < L ? lv[tid][head] : -INFINITY;
+      int bi = head < L ? li[tid][head] : NONE;
+      int bt = tid;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        const int ot = __shfl_xor(bt, o, 64);
+        if (better(ov, oi, bv, bi)) {
+          bv = ov;
+          bi = oi;
+          bt = ot;
+        }
+      }
+      if (lane == 0) {
+        red_v[wave] = bv;
+        red_i[wave] = bi;
+        red_t[wave] = bt;
+      }
+      __syncthreads();
+      if (tid == 0) {
+        float wv = red_v[0];
+        int wi = red_i[0], wt = red_t[0];
+        for (int w = 1; w < NW; ++w)
+          if (better(red_v[w], red_i[w], wv, wi)) {
+            wv = red_v[w];
+            wi = red_i[w];
+            wt = red_t[w];
+          }
+        sel_v[b0 + round] = wv;
+        sel_i[b0 + round] = wi;
+        red_t[0] = wt;
+      }
+      __syncthreads();
+      if (tid == red_t[0]) ++head;
+      __syncthreads();
+    }
+    // the group's live children count their tokens for the groups after it
+    // (at most K - Kg <= BEAM_MAX - 1 distinct tokens in all)
+    if (g + 1 < groups) {
+      if (tid == 0) {
+        int n = np;
+        for (int k = b0; k < b0 + Kg; ++k) {
+          const int si = sel_i[k];
+          if (si == NONE) continue;
+          const int parent = si / vocab, tok = si - parent * vocab;
+          if (!live[parent]) continue;  // a finished beam's carry
+          int p = 0;
+          while (p < n && pen_tok[p] != tok) ++p;
+          if (p < n) {
+            ++pen_cnt[p];
+          } else if (n < BEAM_MAX) {
+            pen_tok[n] = tok;
+            pen_cnt[n] = 1;
+            ++n;
+          }
+          filt[(tok & (DIV_FILTER_BITS - 1)) >> 5] |= 1u << (tok & 31);
+        }
+        pen_n = n;
+      }
+      __syncthreads();
+    }
+  }
+  // 4. new beams: parent = flat / V, token = flat % V; an empty slot carries
+  //    its own row as a finished beam at -inf
+  for (int e = tid; e < K * (t + 2); e += BS_THREADS) {
+    const int k = e / (t + 2), pos = e - k * (t + 2);
+    const bool none = sel_i[k] == NONE;
+    const int parent = none ? k : sel_i[k] / vocab, tok = none ? end_token : sel_i[k] - parent * vocab;
+    const int r = row0 + k, pr = row0 + parent;
+    hist_out[(long long)r * hist_ld + pos] = pos <= t ? hist_in[(long long)pr * hist_ld + pos] : tok;
+    if (pos <= t) src_out[(long long)r * src_ld + pos] = src_in[(long long)pr * src_ld + pos];
+    else if (pos < src_ld) src_out[(long long)r * src_ld + pos] = r;  // next step writes its K/V at row r
+  }
+  int fin = 1;
+  if (tid < K) {
+    const bool none = sel_i[tid] == NONE;
+    const int parent = none ? tid : sel_i[tid] / vocab, tok = none ? end_token : sel_i[tid] - parent * vocab;
+    const bool pfin = none || bfin[parent];
+    fin = pfin || tok == end_token;
+    // the carried score is the unpenalised candidate, from the logit again
+    float s = -INFINITY;
+    if (!none) s = bfin[parent] ? bscore[parent] : logits[(long long)(row0 + parent) * ldl + tok] + coff[parent];
+    tok_out[row0 + tid] = tok;
+    beam_score[row0 + tid] = s;
+    beam_len[row0 + tid] = pfin ? blen[parent] : t + 1;
+    beam_fin[row0 + tid] = fin;
+  }
+  // 5. the image stops once every beam of every group has finished
+  if (__syncthreads_and(fin) && tid == 0) status[img] = 1;
+}
+
 // Ranks an image's beams by score / max(len, 1)^alpha (descending, ties to
 // the lower beam index) and writes the n-best list: tokens after <start>
 // without a final <end>, zero-padded to tok_ld.
@@ -1486,6 +1791,42 @@ int fpnmt_beam_step_log(int n_images, int beam_n, int vocab, const float* logits
                      beam_score, beam_len, beam_fin, hist_in, hist_out, hist_ld, t, src_in, src_out, src_ld,
                      end_token, tok_out, status);
   return check_launch("beam_step_log");
+}
+
+int fpnmt_beam_step_groups(int n_images, int beam_n, int groups, float diversity_penalty, int vocab,
+                           const float* logits, long long ldl, float* beam_score, int32_t* beam_len,
+                           int32_t* beam_fin, const int32_t* hist_in, int32_t* hist_out, int hist_ld, int t,
+                           const int32_t* src_in, int32_t* src_out, int src_ld, int end_token, int32_t* tok_out,
+                           int32_t* status, fpnmt_stream_t stream) {
+  if (n_images <= 0) return 0;
+  if (beam_n <= 0 || beam_n > BEAM_MAX) return fail(FPNMT_E_UNSUPPORTED, "beam_step_groups: 1 <= beam_n <= 16");
+  if (groups < 1 || beam_n % groups != 0)
+    return fail(FPNMT_E_ARG, "beam_step_groups: groups must be >= 1 and divide beam_n");
+  if (!(diversity_penalty >= 0.f) || !std::isfinite(diversity_penalty))
+    return fail(FPNMT_E_ARG, "beam_step_groups: diversity_penalty must be finite and >= 0");
+  if (vocab < beam_n) return fail(FPNMT_E_ARG, "beam_step_groups: vocab < beam_n");
+  if ((long long)beam_n * vocab > 0x7ffffffeLL || ldl < vocab)
+    return fail(FPNMT_E_ARG, "beam_step_groups: beam_n * vocab exceeds int32, or ldl < vocab");
+  if (end_token < 0 || end_token >= vocab)
+    return fail(FPNMT_E_ARG, "beam_step_groups: end_token outside the vocabulary");
+  if (t < 0 || t + 2 > hist_ld || t + 1 > src_ld)
+    return fail(FPNMT_E_ARG, "beam_step_groups: bad position / table widths");
+  if (!logits || !beam_score || !beam_len || !beam_fin || !hist_in || !hist_out || !src_in || !src_out || !tok_out ||
+      !status)
+    return fail(FPNMT_E_ARG, "beam_step_groups: null pointer");
+  const int kg = beam_n / groups;
+#define FPNMT_GROUPS_LAUNCH(LEN)                                                                                    \
+  hipLaunchKernelGGL(beam_step_groups_kernel<LEN>, dim3(n_images), dim3(BS_THREADS), 0, S(stream), beam_n, groups, \
+                     diversity_penalty, vocab, logits, ldl, beam_score, beam_len, beam_fin, hist_in, hist_out,     \
+                     hist_ld, t, src_in, src_out, src_ld, end_token, tok_out, status)
+  // the per-thread list holds the smallest of 1, 2, 4, 8, 16 entries that covers a group
+  if (kg <= 1) FPNMT_GROUPS_LAUNCH(1);
+  else if (kg <= 2) FPNMT_GROUPS_LAUNCH(2);
+  else if (kg <= 4) FPNMT_GROUPS_LAUNCH(4);
+  else if (kg <= 8) FPNMT_GROUPS_LAUNCH(8);
+  else FPNMT_GROUPS_LAUNCH(16);
+#undef FPNMT_GROUPS_LAUNCH
+  return check_launch("beam_step_groups");
 }
 
 int fpnmt_beam_finalize(int n_images, int beam_n, const int32_t* hist, int hist_ld, const float* beam_score,

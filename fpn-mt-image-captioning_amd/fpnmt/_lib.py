@@ -251,6 +251,7 @@ SIGNATURES = {
     "fpnmt_decode_attention": [I, I, I, I, I, F, P, LL, P, LL, LL, LL, LL, P, I, I, P, LL, P],
     "fpnmt_beam_step": [I, I, I, P, LL, P, P, P, I, I, P, P, I, I, P, P, I, P, P, P],
     "fpnmt_beam_step_log": [I, I, I, P, LL, P, P, P, P, P, I, I, P, P, I, I, P, P, P],
+    "fpnmt_beam_step_groups": [I, I, I, F, I, P, LL, P, P, P, P, P, I, I, P, P, I, I, P, P, P],
     "fpnmt_beam_finalize": [I, I, P, I, P, P, P, F, P, I, P, P, P],
     "fpnmt_sample_step": [I, I, P, LL, F, I, F, ULL, P, P, P, P, P, I, I, I, P, P, P],
     "fpnmt_sample_uniform": [I, I, ULL, P, P, P],

@@ -60,6 +60,15 @@ renormalised by the step kernel), then the constraints, then the step kernel:
 scores are log-probabilities under the combined (and then constrained)
 distribution. With an empty `ensemble` the list holds the one model, no call
 is made and the graphs are launch for launch what they were.
+
+Diverse beam search (mode="beam", beam_groups=G > 1): the beam_n rows are G
+groups of beam_n / G contiguous rows; the last launch of a position is
+fpnmt_beam_step_groups instead of fpnmt_beam_step_log, which ranks the groups
+in order, each among its own rows, and takes diversity_penalty off a token's
+candidates for every live beam of an earlier group that took it at this
+position. Scores stay unpenalised log-probability sums; step 0 starts with
+each group's first row at 0. With beam_groups=1 the step is
+fpnmt_beam_step_log and the graphs are launch for launch what they were.
 """
 from __future__ import annotations
 
@@ -352,6 +361,27 @@ class _CachedDecoder:
         self._reset()
 
 
+def beam_groups_validated(mode, beam_n, beam_groups=1, diversity_penalty=0.0):
+    """(beam_groups, diversity_penalty) as (int, float), or ValueError: the
+    groups are for mode="beam", divide beam_n, and a penalty is finite,
+    >= 0 and needs more than one group to act on."""
+    if isinstance(beam_groups, bool) or not isinstance(beam_groups, int):
+        raise ValueError(f"beam_groups must be an int, got {beam_groups!r}")
+    try:
+        lam = float(diversity_penalty)
+    except (TypeError, ValueError):
+        raise ValueError(f"diversity_penalty must be a number, got {diversity_penalty!r}") from None
+    if mode != "beam" and (beam_groups != 1 or lam != 0.0):
+        raise ValueError(f"beam_groups / diversity_penalty need mode='beam', got mode={mode!r}")
+    if beam_groups < 1 or beam_n % beam_groups != 0:
+        raise ValueError(f"beam_groups {beam_groups} must be >= 1 and divide beam_n {beam_n}")
+    if not (lam >= 0.0) or lam == float("inf"):
+        raise ValueError(f"diversity_penalty must be finite and >= 0, got {diversity_penalty!r}")
+    if lam > 0.0 and beam_groups == 1:
+        raise ValueError("diversity_penalty > 0 needs beam_groups > 1: one group has no earlier group to differ from")
+    return beam_groups, lam
+
+
 class BeamDecoder(_CachedDecoder):
     """decode(images) -> list of token-id lists, one per image; in
     mode="beam", decode(images, n_best=k) -> per image the k best
@@ -363,6 +393,16 @@ class BeamDecoder(_CachedDecoder):
     beam's score is the sum of log_softmax over the constrained rows — its
     log-probability under the constrained, renormalised distribution.
     mode="reference" is the reference's own procedure and takes none.
+
+    beam_groups=G > 1 (mode="beam") is diverse beam search: the beam_n rows
+    are G groups of beam_n / G rows, ranked in group order at every position
+    (fpnmt_beam_step_groups); a group's candidate for a token loses
+    diversity_penalty for every live beam of an earlier group that took the
+    token at this position, and only the group's own beams compete for its
+    rows. Scores stay unpenalised log-probability sums. decode(...,
+    group_best=True) returns each group's best (token ids, score) in group
+    order; n_best ranks all beam_n beams as ever. beam_groups=1 is the plain
+    search, launch for launch.
 
     ensemble: further Transformers that decode jointly with `transformer`
     (at most ENSEMBLE_MAX models in all; any depth, width, heads and
@@ -380,10 +420,12 @@ class BeamDecoder(_CachedDecoder):
 
     def __init__(self, transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph=True,
                  mode="reference", length_alpha=0.0, no_repeat_ngram=0, repetition_penalty=1.0, min_len=0,
-                 banned_tokens=(), ensemble=(), ensemble_mode="prob", ensemble_weights=None):
+                 banned_tokens=(), ensemble=(), ensemble_mode="prob", ensemble_weights=None, beam_groups=1,
+                 diversity_penalty=0.0):
         if mode not in ("reference", "beam"):
             raise ValueError(f"mode must be 'reference' or 'beam', got {mode!r}")
         self.mode, self.length_alpha = mode, float(length_alpha)
+        self.beam_groups, self.diversity_penalty = beam_groups_validated(mode, beam_n, beam_groups, diversity_penalty)
         super().__init__(transformer, n_images, beam_n, max_seq_len, start_token, end_token, use_graph,
                          ensemble, ensemble_mode, ensemble_weights)
         self._set_constraints(no_repeat_ngram, repetition_penalty, min_len, banned_tokens, beam_n)
@@ -414,7 +456,8 @@ class BeamDecoder(_CachedDecoder):
         self.tok.fill_(self.start_token)
         if self.mode == "beam":
             self.score.fill_(float("-inf"))
-            self.score.view(self.n_images, self.beam_n)[:, 0] = 0.0
+            # each group's first row starts alone (one group: the image's first row)
+            self.score.view(self.n_images * self.beam_groups, self.beam_n // self.beam_groups)[:, 0] = 0.0
             self.blen.zero_()
             self.fin.zero_()
         else:
@@ -434,6 +477,11 @@ class BeamDecoder(_CachedDecoder):
         if self.mode == "beam":
             if self.constrained:
                 self._constrain(logits, hin, t)
+            if self.beam_groups > 1:
+                call("fpnmt_beam_step_groups", self.n_images, self.beam_n, self.beam_groups, self.diversity_penalty,
+                     self.V, ptr(logits), self.V, ptr(self.score), ptr(self.blen), ptr(self.fin), ptr(hin), ptr(hout),
+                     T + 1, t, ptr(sin), ptr(sout), T, self.end_token, ptr(self.tok), ptr(self.status), s)
+                return
             call("fpnmt_beam_step_log", self.n_images, self.beam_n, self.V, ptr(logits), self.V, ptr(self.score),
                  ptr(self.blen), ptr(self.fin), ptr(hin), ptr(hout), T + 1, t, ptr(sin), ptr(sout), T,
                  self.end_token, ptr(self.tok), ptr(self.status), s)
@@ -444,10 +492,15 @@ class BeamDecoder(_CachedDecoder):
 
     # -------------------------------------------------------------- decode
     @torch.no_grad()
-    def decode(self, images, check_every=8, n_best=1):
+    def decode(self, images, check_every=8, n_best=1, group_best=False):
         """images (n_images, H, W, 3) on the GPU -> list of token-id lists;
         n_best > 1 (mode="beam"): per image a list of the n_best
-        (token-id list, score) pairs, best first."""
+        (token-id list, score) pairs, best first, over all beam_n beams;
+        group_best (mode="beam"): per image beam_groups (token-id list,
+        score) pairs in group order, each its group's best by
+        score / len^length_alpha."""
+        if group_best and (self.mode != "beam" or n_best != 1):
+            raise ValueError("group_best needs mode='beam' and n_best=1: it returns one caption per group")
         if images.shape[0] != self.n_images:
             raise ValueError(f"expected {self.n_images} images, got {images.shape[0]}")
         if n_best < 1 or n_best > (self.beam_n if self.mode == "beam" else 1):
@@ -464,18 +517,28 @@ class BeamDecoder(_CachedDecoder):
             if check_every and (t + 1) % check_every == 0 and t + 1 < self.T and bool(self.status.all()):
                 break
         if self.mode == "beam":
-            return self._nbest(steps, n_best)
+            return self._nbest(steps, n_best, group_best)
         lens = self.result_len.tolist()
         res = self.result.cpu()
         return [res[i, :lens[i]].tolist() for i in range(self.n_images)]
 
-    def _nbest(self, steps, n_best):
+    def _nbest(self, steps, n_best, group_best=False):
         """Rank the beams of every image (fpnmt_beam_finalize over the tables
-        the last step wrote) and read the n-best list back."""
+        the last step wrote) and read the n-best list back. group_best: the
+        same kernel with every group as an image of its own, and the head of
+        each group's list."""
         n, K, T = self.n_images, self.beam_n, self.T
+        if group_best:
+            G = self.beam_groups
+            n, K = n * G, K // G
         call("fpnmt_beam_finalize", n, K, ptr(self.hist[steps % 2]), T + 1, ptr(self.score), ptr(self.blen),
              ptr(self.fin), self.length_alpha, ptr(self.nbest_tok), T, ptr(self.nbest_len), ptr(self.nbest_score),
              stream_ptr())
+        if group_best:
+            tok = self.nbest_tok.view(n, K, T).cpu()
+            lens, score = self.nbest_len.view(n, K).tolist(), self.nbest_score.view(n, K).tolist()
+            return [[(tok[i * G + g, 0, :lens[i * G + g][0]].tolist(), score[i * G + g][0]) for g in range(G)]
+                    for i in range(self.n_images)]
         tok, lens, score = self.nbest_tok.cpu(), self.nbest_len.tolist(), self.nbest_score.tolist()
         if n_best == 1:
             return [tok[i, 0, :lens[i][0]].tolist() for i in range(n)]

@@ -368,7 +368,8 @@ class Pipeline:
     def predict_batch(self, images, max_seq_len=None, beam_n=BEAM_SEARCH_N, use_graph=True, mode="reference",
                       length_alpha=0.0, n_best=1, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None,
                       no_repeat_ngram=0, repetition_penalty=1.0, min_len=0, banned_tokens=(), weights="model",
-                      ensemble=(), ensemble_mode="prob", ensemble_weights=None):
+                      ensemble=(), ensemble_mode="prob", ensemble_weights=None, beam_groups=1, diversity_penalty=0.0,
+                      group_best=False):
         """predict() for a batch of images (n, h, w, 3) at once: the same
         beam procedure per image (pipeline.py:82-154), with a K/V cache and a
         hipGraph per decode step (fpnmt.decode.BeamDecoder). Returns one
@@ -379,6 +380,19 @@ class Pipeline:
         of log-probabilities, finished beams kept, the result ranked by
         score / len^length_alpha. n_best > 1 then returns, per image, the
         n_best (token-id list, score) pairs, best first.
+
+        beam_groups=G > 1 (mode="beam" only; G divides beam_n) makes it a
+        diverse beam search: the beams are G groups of beam_n / G, ranked in
+        group order at every position on the device
+        (fpnmt_beam_step_groups); a group's candidate for a token loses
+        diversity_penalty (>= 0; > 0 needs G > 1) for every live beam of an
+        earlier group that took that token at that position. Scores stay
+        unpenalised log-probability sums, comparable with score_captions.
+        n_best ranks all beam_n beams as ever; group_best=True (with
+        n_best=1) returns, per image, G (token-id list, score) pairs in
+        group order, each the best of its group by score / len^length_alpha.
+        mode="sample" and mode="reference" raise ValueError with any of the
+        three set.
 
         mode="sample" draws n_samples captions per image from the model
         (fpnmt.decode.SampleDecoder: temperature, top_k (0: off), top_p (1:
@@ -426,8 +440,10 @@ class Pipeline:
                 return self.predict_batch(images, max_seq_len, beam_n, use_graph, mode, length_alpha, n_best,
                                           n_samples, temperature, top_k, top_p, seed, no_repeat_ngram,
                                           repetition_penalty, min_len, banned_tokens, ensemble=ensemble,
-                                          ensemble_mode=ensemble_mode, ensemble_weights=ensemble_weights)
-        from fpnmt.decode import BeamDecoder, SampleDecoder
+                                          ensemble_mode=ensemble_mode, ensemble_weights=ensemble_weights,
+                                          beam_groups=beam_groups, diversity_penalty=diversity_penalty,
+                                          group_best=group_best)
+        from fpnmt.decode import BeamDecoder, SampleDecoder, beam_groups_validated
         T = max_seq_len or self.max_seq_len
         try:
             banned = tuple(sorted({int(b) for b in banned_tokens}))
@@ -447,6 +463,10 @@ class Pipeline:
             from fpnmt.decode import ensemble_weights_normalised
             ekey = ("ensemble", tuple(id(m) for m in members), ensemble_mode,
                     ensemble_weights_normalised(1 + len(members), ensemble_weights))
+        # checked here too: mode="sample" builds no BeamDecoder, and a cached decoder would not see the arguments
+        groups, lam = beam_groups_validated(mode, beam_n, beam_groups, diversity_penalty)
+        if group_best and mode != "beam":
+            raise ValueError(f"group_best needs mode='beam', got mode={mode!r}")
         if mode == "sample":
             key = (images.shape[0], n_samples, T, use_graph, mode, float(temperature), top_k, float(top_p)) + ckey
             key += ekey
@@ -461,12 +481,15 @@ class Pipeline:
         if ckey != (0, 1.0, 0, ()):  # an unconstrained decoder keeps the key it always had
             key += ckey
         key += ekey
+        if (groups, lam) != (1, 0.0):  # a plain beam search keeps the key it always had
+            key += ("groups", groups, lam)
         dec = getattr(self, "_decoders", {}).get(key)
         if dec is None:
             dec = BeamDecoder(self.transformer, images.shape[0], beam_n, T, self.start_token, self.end_token,
-                              use_graph=use_graph, mode=mode, length_alpha=length_alpha, **cons, **ens)
+                              use_graph=use_graph, mode=mode, length_alpha=length_alpha, beam_groups=groups,
+                              diversity_penalty=lam, **cons, **ens)
             self.__dict__.setdefault("_decoders", {})[key] = dec
-        return dec.decode(images, n_best=n_best)
+        return dec.decode(images, n_best=n_best, group_best=group_best)
 
     def load_member(self, path, n_layers=None, backbone=None, rate=0.0):
         """A model-only checkpoint (ckpt.write / ckpt.export_ema of any

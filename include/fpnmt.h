@@ -21,6 +21,7 @@
  *   fpnmt_decode_attention scaled_dot_product_attention, last query row   utils/pipeline.py:105-113
  *   fpnmt_beam_step        softmax + top_k + gather + argmax of predict   utils/pipeline.py:115-147
  *   fpnmt_beam_step_log, fpnmt_beam_finalize   beam search proper (log-prob beams, n-best)   not in the reference
+ *   fpnmt_beam_step_groups                     diverse beam search (beam groups, Hamming penalty) not in the reference
  *   fpnmt_sample_step, fpnmt_sample_uniform    sampled decoding (temperature, top-k, top-p)    not in the reference
  *   fpnmt_logits_constrain                     n-gram blocking, repetition penalty, min length  not in the reference
  *   fpnmt_ciderd_reward, fpnmt_scst_pack       CIDEr-D reward and advantages on the device     not in the reference
@@ -1026,6 +1027,37 @@ int fpnmt_beam_step_log(int n_images, int beam_n, int vocab, const float* logits
 int fpnmt_beam_finalize(int n_images, int beam_n, const int32_t* hist, int hist_ld, const float* beam_score,
                         const int32_t* beam_len, const int32_t* beam_fin, float alpha, int32_t* nbest_tok,
                         int tok_ld, int32_t* nbest_len, float* nbest_score, fpnmt_stream_t stream);
+/* Diverse beam search (Vijayakumar et al.): fpnmt_beam_step_log's step with
+ * the image's beam_n rows split into `groups` groups of Kg = beam_n / groups
+ * contiguous rows (group g: rows g*Kg .. (g+1)*Kg - 1), ranked in group
+ * order at every position. cnt[token] starts empty at every position.
+ *   live row b of group g: token j is offered at
+ *     (logits[b][j] + coff[b]) - diversity_penalty * cnt[j],
+ *     coff[b] = beam_score[b] - logsumexp(logits row b); the product is an
+ *     fp32 product, subtracted after the add;
+ *   finished row b: one candidate, beam_score[b] at j = end_token, never
+ *     penalised and never counted;  row at -inf: none.
+ * Only the rows of group g compete; order and flat index (b*vocab + j, b the
+ * row inside the image) as in fpnmt_beam_step_log. Group g takes its Kg best
+ * into its own rows, best first, and every live child that took token j
+ * (<end> included) adds 1 to cnt[j] for the groups after it.
+ * A live child's beam_score is the UNPENALISED logits[b][j] + coff[b]: scores
+ * stay sums of log-probabilities. beam_len / beam_fin / hist_out / src_out /
+ * tok_out, the slot without a candidate and the frozen image are those of
+ * fpnmt_beam_step_log; status[img] = 1 once all beam_n rows have finished.
+ * The caller starts step 0 with score 0 on each GROUP's first row and -inf
+ * on the others. groups == 1 writes what fpnmt_beam_step_log writes, byte
+ * for byte, whatever the penalty; diversity_penalty == 0 writes what
+ * fpnmt_beam_step_log(n_images * groups, Kg, ...) writes on the same buffers
+ * (status apart). fpnmt_beam_finalize(n_images * groups, Kg, ...) ranks each
+ * group on its own.
+ * Requires what fpnmt_beam_step_log requires; FPNMT_E_ARG also for
+ * groups < 1, beam_n % groups != 0, and a negative or non-finite penalty.  */
+int fpnmt_beam_step_groups(int n_images, int beam_n, int groups, float diversity_penalty, int vocab,
+                           const float* logits, long long ldl, float* beam_score, int32_t* beam_len,
+                           int32_t* beam_fin, const int32_t* hist_in, int32_t* hist_out, int hist_ld, int t,
+                           const int32_t* src_in, int32_t* src_out, int src_ld, int end_token, int32_t* tok_out,
+                           int32_t* status, fpnmt_stream_t stream);
 
 /* Sampled decoding (not in the reference): the last launch of a decode step
  * that draws one token per row from its fp32 logits. Rows are independent
