@@ -259,6 +259,7 @@ SIGNATURES = {
     "fpnmt_logits_ensemble": [I, I, I, PP, C.POINTER(LL), C.POINTER(F), I, P, P, LL, P],
     "fpnmt_ciderd_reward": [P, I, I, P, I, P, P, P, P, P],  # fpnmt_cider_tables*: fpnmt.cider_device.CiderTables
     "fpnmt_scst_pack": [I, I, I, P, P, P, I, P, P, P, I, I, I, P, I, P, P, P],
+    "fpnmt_ciderd_consensus": [P, I, I, P, I, P, P, P, P, P, P, P],
     "fpnmt_bn_stats": [I, LL, I, P, P, P, P, P, F, P],
     "fpnmt_bn_apply": [I, LL, I, P, P, P, P, P, F, I, P, P, P],
     "fpnmt_bn_bwd": [I, LL, I, P, P, P, P, F, I, P, P, P, P, P, P],
@@ -313,6 +314,8 @@ SAMPLE_FILTER_MAX_VOCAB = 16384  # FPNMT_SAMPLE_FILTER_MAX_VOCAB
 CONSTRAIN_MAX_LEN, CONSTRAIN_MAX_BANNED = 1024, 4096  # FPNMT_CONSTRAIN_MAX_*
 ENSEMBLE_MAX = 8  # FPNMT_ENSEMBLE_MAX
 CIDER_MAX_LEN = 128  # FPNMT_CIDER_MAX_LEN
+CONSENSUS_MAX_CANDS = 64  # FPNMT_CONSENSUS_MAX_CANDS
+CONSENSUS_LDS_BYTES = 160 * 1024  # fpnmt_ciderd_consensus keeps an image's candidates in one work-group's LDS
 SCST_MEAN, SCST_GREEDY = 0, 1  # FPNMT_SCST_*
 
 

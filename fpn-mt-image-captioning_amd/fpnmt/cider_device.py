@@ -28,6 +28,13 @@ with numpy, which lets them be checked without a GPU.
 
 The intended use is ONE instance over the whole training set, with
 image_keys naming each batch's images (SelfCriticalTrainer.step).
+
+The same document table serves consensus (minimum-Bayes-risk) selection
+among an image's candidate captions (fpnmt_ciderd_consensus): there the
+"references" are the other candidates, so only df_keys / df_idf, idf_absent
+and the Gaussian table are read. `consensus` is the launch, `consensus_host`
+/ `pairwise_host` walk the packed arrays with numpy, `consensus_check` says
+before any device work whether a shape is served.
 """
 from __future__ import annotations
 
@@ -261,7 +268,104 @@ class DeviceCiderD:
         return np.array([self._score_one(int(i), c) for i, cs in zip(image_index, candidates) for c in cs],
                         dtype=np.float64)
 
+    def _cand_vec(self, cand):
+        """A candidate's distinct packed keys (ascending), tf * idf, orders,
+        four norms and length (the bigram count), from the document table."""
+        a = self.np
+        cand = [int(t) for t in cand]
+        keys = np.concatenate([pack_keys(cand, k) for k in range(1, 5)]) if cand else np.zeros(0, dtype=np.uint64)
+        ck, tf = np.unique(keys, return_counts=True)
+        pos = np.searchsorted(a["df_keys"], ck)
+        pos_c = np.minimum(pos, max(len(a["df_keys"]) - 1, 0))
+        hit = (pos < len(a["df_keys"])) & (a["df_keys"][pos_c] == ck) if len(a["df_keys"]) else np.zeros(len(ck), bool)
+        idf = np.where(hit, a["df_idf"][pos_c] if len(a["df_idf"]) else 0.0, self.idf_absent)
+        w = tf.astype(np.float64) * idf
+        od = key_order(ck) - 1
+        return ck, w, od, np.sqrt(np.bincount(od, weights=w * w, minlength=4)), int(tf[od == 1].sum())
+
+    def pairwise_host(self, candidates):
+        """CiderDReward.pairwise restated on the packed document table: (n,
+        n) float64, [s][j] = the CIDEr-D of candidate s with candidate j as
+        its only reference. The same keys, searches and clipping as
+        fpnmt_ciderd_consensus."""
+        for c in candidates:
+            if len(c) > self.max_len:
+                raise ValueError(f"a candidate of {len(c)} tokens exceeds max_len {self.max_len}")
+        vecs = [self._cand_vec(c) for c in candidates]
+        gauss = self.np["gauss"]
+        out = np.zeros((len(vecs), len(vecs)), dtype=np.float64)
+        for s, (hk, hw, hod, nh, lh) in enumerate(vecs):
+            for j, (rk, rw, _, nr, lr) in enumerate(vecs):
+                if not len(hk) or not len(rk):
+                    continue
+                p = np.searchsorted(rk, hk)
+                pc = np.minimum(p, len(rk) - 1)
+                r = np.where((p < len(rk)) & (rk[pc] == hk), rw[pc], 0.0)
+                val = np.bincount(hod, weights=np.minimum(hw, r) * r, minlength=4)
+                for k in range(4):
+                    if nh[k] != 0 and nr[k] != 0:
+                        val[k] /= nh[k] * nr[k]
+                    val[k] *= gauss[abs(lh - lr)]
+                out[s, j] = float(np.mean(val) * 10.0)
+        return out
+
+    def consensus_host(self, candidates_per_image, weights=None):
+        """CiderDReward.consensus restated on the packed tables, per image:
+        candidates_per_image[i] are image i's candidate token-id lists,
+        weights[i] (optional) their non-negative weights -> a list of (util
+        float64[n_i], pick) pairs. Checks the packing without a GPU."""
+        from utils.cider_reward import consensus_of
+        if weights is not None and len(weights) != len(candidates_per_image):
+            raise ValueError(f"{len(weights)} weight rows for {len(candidates_per_image)} images")
+        return [consensus_of(self.pairwise_host(cs), None if weights is None else weights[i])
+                for i, cs in enumerate(candidates_per_image)]
+
     # ---------------------------------------------------------------- launch
+    @staticmethod
+    def consensus_lds_bytes(n, max_tokens):
+        """The LDS fpnmt_ciderd_consensus needs for n candidates of up to
+        max_tokens tokens (include/fpnmt.h): at most CONSENSUS_LDS_BYTES."""
+        e = sum(max(max_tokens - k, 0) for k in range(4))
+        return 16 * n * e + 64 * e + 44 * n
+
+    def consensus_check(self, n, max_tokens, device=None):
+        """ValueError unless fpnmt_ciderd_consensus serves n candidates per
+        image of up to max_tokens tokens from these tables (on `device`, when
+        given). Raises before any device work."""
+        import torch
+        from ._lib import CONSENSUS_LDS_BYTES, CONSENSUS_MAX_CANDS
+        if self.device.type == "cpu":
+            raise ValueError("consensus needs DeviceCiderD tables built on the GPU (from_corpus(..., device=...))")
+        if device is not None:
+            device = torch.device(device)
+            if device.type != self.device.type or (device.index is not None and device.index != self.device.index):
+                raise ValueError(f"the consensus tables live on {self.device}, the decoder on {device}")
+        if not 1 <= n <= CONSENSUS_MAX_CANDS:
+            raise ValueError(f"consensus serves 1..{CONSENSUS_MAX_CANDS} candidates per image, got {n}")
+        if max_tokens > self.max_len:
+            raise ValueError(f"captions of up to {max_tokens} tokens exceed the consensus tables' max_len "
+                             f"{self.max_len}")
+        need = self.consensus_lds_bytes(n, max_tokens)
+        if need > CONSENSUS_LDS_BYTES:
+            raise ValueError(f"consensus over {n} candidates of up to {max_tokens} tokens needs {need} bytes of LDS, "
+                             f"above the {CONSENSUS_LDS_BYTES} of a work-group: fewer candidates or a shorter "
+                             "max_seq_len")
+
+    def consensus(self, hist, len, fin, n, util, pick, weight=None, pair=None):
+        """fpnmt_ciderd_consensus over pick.numel() images of n candidate
+        rows each, laid out as the sampler and the beam search leave them
+        (row r's caption is hist[r][1 : 1 + len[r] - fin[r]]): util (f64,
+        rows) the consensus utilities, pick (int32, images) the index of the
+        greatest per image; weight (f64, rows; None: uniform) the candidates'
+        non-negative weights, pair (f64, images * n * n; None: not wanted)
+        every sim(c_s, c_j). At most CONSENSUS_MAX_CANDS candidates whose keys
+        fit one work-group's LDS (consensus_lds_bytes(n, hist.shape[1] - 1) <=
+        CONSENSUS_LDS_BYTES). No allocation, no synchronisation, capturable."""
+        from ._lib import call, ptr, stream_ptr
+        call("fpnmt_ciderd_consensus", C.byref(self.tables), pick.numel(), n, ptr(hist), hist.stride(0), ptr(len),
+             ptr(fin), ptr(weight), ptr(util), ptr(pick), ptr(pair), stream_ptr())
+        return util, pick
+
     def reward(self, hist, slen, fin, img_index, n, out):
         """fpnmt_ciderd_reward over out.numel() caption rows (n per image):
         out[r] (f64) = the CIDEr-D of hist[r][1 : 1 + slen[r] - fin[r]]

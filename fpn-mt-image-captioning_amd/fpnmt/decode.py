@@ -69,6 +69,14 @@ candidates for every live beam of an earlier group that took it at this
 position. Scores stay unpenalised log-probability sums; step 0 starts with
 each group's first row at 0. With beam_groups=1 the step is
 fpnmt_beam_step_log and the graphs are launch for launch what they were.
+
+Consensus decoding (mode="beam" and SampleDecoder; decode(consensus=...)): a
+post-processing of one decode, not a property of the decoder. After the
+position loop, outside the per-position graphs, one fpnmt_ciderd_consensus
+scores an image's beam_n / n_samples candidate rows against each other under
+CIDEr-D on the decoder's own hist / len / fin tables and picks the one of
+greatest utility; the utilities and picks join the read-back the decode does
+anyway. Without `consensus` no launch is added and nothing is allocated.
 """
 from __future__ import annotations
 
@@ -113,6 +121,44 @@ def ensemble_weights_normalised(n_models, weights):
     return tuple(x / total for x in w)
 
 
+CONSENSUS_WEIGHTS = ("uniform", "posterior")
+
+
+def consensus_validated(mode, consensus, consensus_weights="uniform", consensus_all=False, n=1, max_seq_len=1,
+                        device=None, n_best=1, group_best=False):
+    """The consensus arguments of a decode -> whether a consensus launch
+    follows it; ValueError names what does not fit. consensus: None, or the
+    DeviceCiderD whose corpus supplies the idf; n candidates per image of up
+    to max_seq_len tokens on `device`. Touches no device."""
+    if consensus is None:
+        if consensus_weights != "uniform" or consensus_all:
+            raise ValueError(f"consensus_weights={consensus_weights!r} / consensus_all={consensus_all!r} given "
+                             "without consensus= (the DeviceCiderD tables)")
+        return False
+    if mode not in ("beam", "sample"):
+        raise ValueError(f"consensus needs several candidates per image: mode='beam' or mode='sample', got {mode!r}")
+    if n_best != 1 or group_best:
+        raise ValueError("consensus ranks all candidates itself: it takes neither n_best > 1 nor group_best "
+                         "(consensus_all=True returns every candidate)")
+    if consensus_weights not in CONSENSUS_WEIGHTS:
+        raise ValueError(f"consensus_weights must be one of {CONSENSUS_WEIGHTS}, got {consensus_weights!r}")
+    check = getattr(consensus, "consensus_check", None)
+    if check is None:
+        raise ValueError(f"consensus must be a fpnmt.cider_device.DeviceCiderD, got {type(consensus).__name__}")
+    check(n, max_seq_len, device)
+    return True
+
+
+def consensus_ranked(ids, score, util, pick, consensus_all):
+    """One image's candidates (token-id lists, scores, utilities in row
+    order) -> the chosen ids, or with consensus_all every (ids, score,
+    utility) by utility descending, then index."""
+    if not consensus_all:
+        return ids[pick]
+    order = sorted(range(len(ids)), key=lambda r: (-util[r], r))
+    return [(ids[r], score[r], util[r]) for r in order]
+
+
 class _Model:
     """What belongs to ONE model of a decoder: the Transformer, its geometry,
     and (filled by the decoder) its K/V cache `kv`, cross K/V `enc_kv` with
@@ -152,6 +198,23 @@ class _CachedDecoder:
         self.use_graph = use_graph
         self.dt = None
         self.graphs = None
+        self.cons_util = self.cons_pick = None  # allocated by the first consensus launch
+
+    # ----------------------------------------------------------- consensus
+    def _consensus(self, tables, weights, hist, lens, fin, score):
+        """One fpnmt_ciderd_consensus over the decoder's own state (beam_n
+        candidate rows per image), after the position loop and outside its
+        graphs. "posterior": the candidates weigh softmax(score) per image,
+        in fp64, computed by torch on the device (a dead beam's -inf gives
+        0); "uniform" passes no weights. Returns the device tensors util
+        (R,) f64 and pick (n_images,) int32."""
+        if self.cons_util is None:
+            self.cons_util = torch.zeros(self.R, dtype=torch.float64, device=hist.device)
+            self.cons_pick = torch.zeros(self.n_images, dtype=torch.int32, device=hist.device)
+        w = None
+        if weights == "posterior":
+            w = torch.softmax(score.double().view(self.n_images, self.beam_n), dim=1).reshape(-1).contiguous()
+        return tables.consensus(hist, lens, fin, self.beam_n, self.cons_util, self.cons_pick, weight=w)
 
     # ------------------------------------------------------------ ensemble
     def _set_ensemble(self, ensemble, mode, weights):
@@ -492,13 +555,24 @@ class BeamDecoder(_CachedDecoder):
 
     # -------------------------------------------------------------- decode
     @torch.no_grad()
-    def decode(self, images, check_every=8, n_best=1, group_best=False):
+    def decode(self, images, check_every=8, n_best=1, group_best=False, consensus=None,
+               consensus_weights="uniform", consensus_all=False):
         """images (n_images, H, W, 3) on the GPU -> list of token-id lists;
         n_best > 1 (mode="beam"): per image a list of the n_best
         (token-id list, score) pairs, best first, over all beam_n beams;
         group_best (mode="beam"): per image beam_groups (token-id list,
         score) pairs in group order, each its group's best by
-        score / len^length_alpha."""
+        score / len^length_alpha.
+
+        consensus (mode="beam"; a DeviceCiderD on this device): instead of
+        the best-scoring beam, per image the beam that agrees most with the
+        image's other beams under CIDEr-D with the tables' idf
+        (fpnmt_ciderd_consensus, one launch after the position loop on the
+        decoder's own tables). consensus_weights "uniform" weighs the beams
+        equally, "posterior" by the fp64 softmax per image of the scores
+        this decoder returns (score / len^length_alpha). consensus_all: per
+        image every beam as (token ids, score, utility), by utility
+        descending, then beam index."""
         if group_best and (self.mode != "beam" or n_best != 1):
             raise ValueError("group_best needs mode='beam' and n_best=1: it returns one caption per group")
         if images.shape[0] != self.n_images:
@@ -506,6 +580,8 @@ class BeamDecoder(_CachedDecoder):
         if n_best < 1 or n_best > (self.beam_n if self.mode == "beam" else 1):
             raise ValueError(f"n_best {n_best}: mode {self.mode!r} with {self.beam_n} beams gives 1.."
                              f"{self.beam_n if self.mode == 'beam' else 1}")
+        with_consensus = consensus_validated(self.mode, consensus, consensus_weights, consensus_all, self.beam_n,
+                                             self.T, images.device, n_best, group_best)
         self._prepare(images)
         steps = 0
         for t in range(self.T):
@@ -516,6 +592,8 @@ class BeamDecoder(_CachedDecoder):
             steps = t + 1
             if check_every and (t + 1) % check_every == 0 and t + 1 < self.T and bool(self.status.all()):
                 break
+        if with_consensus:
+            return self._consensus_result(steps, consensus, consensus_weights, consensus_all)
         if self.mode == "beam":
             return self._nbest(steps, n_best, group_best)
         lens = self.result_len.tolist()
@@ -543,6 +621,26 @@ class BeamDecoder(_CachedDecoder):
         if n_best == 1:
             return [tok[i, 0, :lens[i][0]].tolist() for i in range(n)]
         return [[(tok[i, k, :lens[i][k]].tolist(), score[i][k]) for k in range(n_best)] for i in range(n)]
+
+    def _consensus_result(self, steps, tables, weights, consensus_all):
+        """The beams in ROW order with the scores n_best would give them
+        (fpnmt_beam_finalize with every row an image of one beam: nothing is
+        ranked, and the score is that kernel's own arithmetic), the consensus
+        launch over the tables the last step wrote, and the one read-back."""
+        n, K, T = self.n_images, self.beam_n, self.T
+        hist = self.hist[steps % 2]
+        call("fpnmt_beam_finalize", n * K, 1, ptr(hist), T + 1, ptr(self.score), ptr(self.blen), ptr(self.fin),
+             self.length_alpha, ptr(self.nbest_tok), T, ptr(self.nbest_len), ptr(self.nbest_score), stream_ptr())
+        util, pick = self._consensus(tables, weights, hist, self.blen, self.fin, self.nbest_score)
+        tok, lens, score = self.nbest_tok.view(n * K, T).cpu(), self.nbest_len.view(-1).tolist(), \
+            self.nbest_score.view(-1).tolist()
+        util, pick = util.tolist(), pick.tolist()
+        out = []
+        for i in range(n):
+            rows = range(i * K, (i + 1) * K)
+            out.append(consensus_ranked([tok[r, :lens[r]].tolist() for r in rows], [score[r] for r in rows],
+                                        [util[r] for r in rows], pick[i], consensus_all))
+        return out
 
 
 class SampleDecoder(_CachedDecoder):
@@ -618,12 +716,27 @@ class SampleDecoder(_CachedDecoder):
              self.end_token, ptr(self.tok), None, stream_ptr())
 
     @torch.no_grad()
-    def decode(self, images, seed=None, check_every=8):
+    def decode(self, images, seed=None, check_every=8, consensus=None, consensus_weights="uniform",
+               consensus_all=False):
         """images (n_images, H, W, 3) on the GPU -> per image a list of
         n_samples (token-id list, log-probability) pairs. seed None: a
-        counter that advances per call; the same seed gives the same draws."""
+        counter that advances per call; the same seed gives the same draws.
+
+        consensus (a DeviceCiderD on this device): per image ONE token-id
+        list, the sample that agrees most with the image's other samples
+        under CIDEr-D with the tables' idf — a Monte Carlo estimate of the
+        caption of greatest expected CIDEr-D (fpnmt_ciderd_consensus, one
+        launch after the position loop on the decoder's own state).
+        consensus_weights "uniform" weighs the samples equally (they are
+        draws from the model already), "posterior" by the fp64 softmax per
+        image of their log-probabilities. consensus_all: per image every
+        sample as (token ids, log-probability, utility), by utility
+        descending, then sample index. The draws are those of the same call
+        without consensus."""
         if images.shape[0] != self.n_images:
             raise ValueError(f"expected {self.n_images} images, got {images.shape[0]}")
+        with_consensus = consensus_validated("sample", consensus, consensus_weights, consensus_all, self.n_samples,
+                                             self.T, images.device)
         if seed is None:
             seed = self._calls
         self._calls += 1
@@ -636,11 +749,19 @@ class SampleDecoder(_CachedDecoder):
                 self._step(t)
             if check_every and (t + 1) % check_every == 0 and t + 1 < self.T and bool(self.fin.all()):
                 break
+        if with_consensus:
+            util, pick = self._consensus(consensus, consensus_weights, self.hist, self.slen, self.fin, self.score)
         hist, lens = self.hist.tolist(), self.slen.tolist()
         fin, score = self.fin.tolist(), self.score.tolist()
+        if with_consensus:
+            util, pick = util.tolist(), pick.tolist()
         out = []
         for i in range(self.n_images):
             rows = range(i * self.n_samples, (i + 1) * self.n_samples)
+            if with_consensus:
+                out.append(consensus_ranked([hist[r][1:1 + lens[r] - fin[r]] for r in rows], [score[r] for r in rows],
+                                            [util[r] for r in rows], pick[i], consensus_all))
+                continue
             out.append([(hist[r][1:1 + lens[r] - fin[r]], score[r]) for r in rows])
         return out
 

@@ -24,6 +24,31 @@ def ngram_counts(ids, n):
     return counts
 
 
+def consensus_of(pair, weights=None):
+    """The consensus utilities and the pick from an (n, n) similarity matrix
+    (CiderDReward.consensus states the definition): plain float64 sums over
+    ascending j."""
+    n = len(pair)
+    p = [1.0] * n if weights is None else [float(w) for w in weights]
+    if len(p) != n:
+        raise ValueError(f"{len(p)} weights for {n} candidates")
+    if any(not w >= 0.0 for w in p):
+        raise ValueError(f"consensus weights must be non-negative, got {p}")
+    util = np.zeros(n, dtype=np.float64)
+    for s in range(n):
+        num = den = 0.0
+        for j in range(n):
+            if j != s:
+                num += p[j] * float(pair[s][j])
+                den += p[j]
+        util[s] = num / den if den != 0.0 else 0.0
+    pick = 0
+    for s in range(1, n):
+        if util[s] > util[pick]:
+            pick = s
+    return util, pick
+
+
 class CiderDReward:
     def __init__(self, df, n_images, refs, n=4, sigma=6.0):
         self._n, self._sigma = n, sigma
@@ -93,6 +118,29 @@ class CiderDReward:
         if len(image_keys) != len(candidates):
             raise ValueError(f"{len(image_keys)} image keys for {len(candidates)} candidate lists")
         return np.array([self.score_one(k, c) for k, cs in zip(image_keys, candidates) for c in cs], dtype=np.float64)
+
+    # ---- consensus (minimum-Bayes-risk) selection among an image's candidates
+    def pairwise(self, candidates):
+        """(n, n) float64: [s][j] = sim(c_s, c_j), the CIDEr-D of candidate s
+        with candidate j as its ONLY reference (score_one's arithmetic on the
+        two _vec's; the corpus supplies the idf). Not symmetric; the diagonal
+        is the self-similarity."""
+        vecs = [self._vec(ngram_counts([int(t) for t in c], self._n)) for c in candidates]
+        out = np.zeros((len(vecs), len(vecs)), dtype=np.float64)
+        for s, (vh, nh, lh) in enumerate(vecs):
+            for j, (vr, nr, lr) in enumerate(vecs):
+                out[s, j] = float(np.mean(self._sim(vh, vr, nh, nr, lh, lr)) / 1 * 10.0)
+        return out
+
+    def consensus(self, candidates, weights=None):
+        """(util, pick): util[s] = sum_{j != s} p_j sim(c_s, c_j) / sum_{j !=
+        s} p_j over ascending j (0 where the denominator is 0; p = weights,
+        non-negative, None: all 1); pick = the index of the greatest util,
+        ties to the lowest. Self is excluded by INDEX: a duplicate at another
+        index counts, so for samples util is a Monte Carlo estimate of the
+        expected CIDEr-D. An empty caption has utility 0 and contributes 0;
+        one candidate alone has utility 0."""
+        return consensus_of(self.pairwise(candidates), weights)
 
     def __call__(self, image_key, candidate):
         return self.score_one(image_key, candidate)

@@ -369,7 +369,7 @@ class Pipeline:
                       length_alpha=0.0, n_best=1, n_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None,
                       no_repeat_ngram=0, repetition_penalty=1.0, min_len=0, banned_tokens=(), weights="model",
                       ensemble=(), ensemble_mode="prob", ensemble_weights=None, beam_groups=1, diversity_penalty=0.0,
-                      group_best=False):
+                      group_best=False, consensus=None, consensus_weights="uniform", consensus_all=False):
         """predict() for a batch of images (n, h, w, 3) at once: the same
         beam procedure per image (pipeline.py:82-154), with a K/V cache and a
         hipGraph per decode step (fpnmt.decode.BeamDecoder). Returns one
@@ -434,7 +434,31 @@ class Pipeline:
         decoder keeps its members alive. weights="ema" exchanges this
         pipeline's model only, never a member; a model and its own average
         share storage, so to ensemble the two, export_ema the average and
-        load_member it."""
+        load_member it.
+
+        consensus (mode="beam" and mode="sample"): a
+        fpnmt.cider_device.DeviceCiderD on the images' device makes the
+        decode a consensus (minimum-Bayes-risk) decode under CIDEr-D, the
+        self-critical reward: per image the candidate (of the beam_n beams or
+        the n_samples draws) that agrees most with the others,
+        util(s) = sum_{j != s} p_j sim(c_s, c_j) / sum_{j != s} p_j with
+        sim the CIDEr-D of c_s against c_j as its only reference under the
+        tables' idf, scored and picked on the device
+        (fpnmt_ciderd_consensus) before the decode's one read-back. Returns
+        one token-id list per image; consensus_all=True returns, per image,
+        every candidate as (token-id list, score, utility) by utility
+        descending, then index, the scores exactly those of the call without
+        consensus (n_best=beam_n / the samples). consensus_weights:
+        "uniform" (p = 1) or "posterior" (p = the fp64 softmax per image of
+        those scores). The three are post-processing of a decode: decoders,
+        their cache keys and graphs are the ones the call without them uses,
+        and weights="ema" and ensemble apply as ever. ValueError:
+        mode="reference", n_best > 1 or group_best with consensus;
+        consensus_weights or consensus_all without it; tables on another
+        device (or built for the host only); max_seq_len above the tables'
+        max_len; more than fpnmt._lib.CONSENSUS_MAX_CANDS candidates, or
+        candidates whose n-gram keys exceed one work-group's LDS
+        (DeviceCiderD.consensus_lds_bytes)."""
         if weights != "model":
             with self._weights(weights):
                 return self.predict_batch(images, max_seq_len, beam_n, use_graph, mode, length_alpha, n_best,
@@ -442,9 +466,16 @@ class Pipeline:
                                           repetition_penalty, min_len, banned_tokens, ensemble=ensemble,
                                           ensemble_mode=ensemble_mode, ensemble_weights=ensemble_weights,
                                           beam_groups=beam_groups, diversity_penalty=diversity_penalty,
-                                          group_best=group_best)
-        from fpnmt.decode import BeamDecoder, SampleDecoder, beam_groups_validated
+                                          group_best=group_best, consensus=consensus,
+                                          consensus_weights=consensus_weights, consensus_all=consensus_all)
+        from fpnmt.decode import BeamDecoder, SampleDecoder, beam_groups_validated, consensus_validated
         T = max_seq_len or self.max_seq_len
+        # checked before a decoder is built; they go to decode(), never into a decoder's key
+        cons_kw = {}
+        if consensus_validated(mode, consensus, consensus_weights, consensus_all,
+                               n_samples if mode == "sample" else beam_n, T, getattr(images, "device", None),
+                               n_best, group_best):
+            cons_kw = dict(consensus=consensus, consensus_weights=consensus_weights, consensus_all=consensus_all)
         try:
             banned = tuple(sorted({int(b) for b in banned_tokens}))
         except (TypeError, ValueError):
@@ -476,7 +507,7 @@ class Pipeline:
                                     use_graph=use_graph, temperature=temperature, top_k=top_k, top_p=top_p, **cons,
                                     **ens)
                 self.__dict__.setdefault("_decoders", {})[key] = dec
-            return dec.decode(images, seed=seed)
+            return dec.decode(images, seed=seed, **cons_kw)
         key = (images.shape[0], beam_n, T, use_graph, mode, float(length_alpha))
         if ckey != (0, 1.0, 0, ()):  # an unconstrained decoder keeps the key it always had
             key += ckey
@@ -489,7 +520,52 @@ class Pipeline:
                               use_graph=use_graph, mode=mode, length_alpha=length_alpha, beam_groups=groups,
                               diversity_penalty=lam, **cons, **ens)
             self.__dict__.setdefault("_decoders", {})[key] = dec
-        return dec.decode(images, n_best=n_best, group_best=group_best)
+        return dec.decode(images, n_best=n_best, group_best=group_best, **cons_kw)
+
+    def consensus_captions(self, captions_per_image, tables, weights=None):
+        """Consensus selection among externally supplied candidates (the
+        union of several decodes, say): captions_per_image[i] are image i's
+        candidate token-id lists, the same number n for every image; tables
+        a fpnmt.cider_device.DeviceCiderD on the GPU; weights None (uniform)
+        or per image n non-negative numbers. The candidates are packed on
+        the host into the sampler's layout (<start>, the tokens; len = their
+        number, fin = 0) and scored by one fpnmt_ciderd_consensus. Returns
+        (pick, util): per image the index of the caption of greatest
+        utility (ties to the lowest), and per image its n utilities
+        (predict_batch states the definition)."""
+        import numpy as np
+        caps = [[[int(t) for t in c] for c in cs] for cs in captions_per_image]
+        b = len(caps)
+        if b == 0:
+            return [], []
+        n = len(caps[0])
+        if any(len(cs) != n for cs in caps):
+            raise ValueError(f"consensus_captions: every image needs the same number of candidates, got "
+                             f"{sorted({len(cs) for cs in caps})}")
+        longest = max([len(c) for cs in caps for c in cs] + [1])
+        if not hasattr(tables, "consensus_check"):
+            raise ValueError(f"consensus_captions: tables must be a fpnmt.cider_device.DeviceCiderD, got "
+                             f"{type(tables).__name__}")
+        tables.consensus_check(n, longest)
+        w = None
+        if weights is not None:
+            w = np.asarray(weights, dtype=np.float64)
+            if w.shape != (b, n) or not np.all(w >= 0.0):
+                raise ValueError(f"consensus_captions: weights must be {b} x {n} non-negative numbers")
+        hist = np.zeros((b * n, longest + 1), dtype=np.int32)
+        hist[:, 0] = self.start_token
+        lens = np.zeros(b * n, dtype=np.int32)
+        for r, c in enumerate(c for cs in caps for c in cs):
+            hist[r, 1:1 + len(c)] = c
+            lens[r] = len(c)
+        dev = tables.device
+        hist, lens = torch.from_numpy(hist).to(dev), torch.from_numpy(lens).to(dev)
+        util = torch.zeros(b * n, dtype=torch.float64, device=dev)
+        pick = torch.zeros(b, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            tables.consensus(hist, lens, torch.zeros_like(lens), n, util, pick,
+                             weight=None if w is None else torch.from_numpy(w.reshape(-1)).to(dev))
+        return pick.tolist(), util.view(b, n).tolist()
 
     def load_member(self, path, n_layers=None, backbone=None, rate=0.0):
         """A model-only checkpoint (ckpt.write / ckpt.export_ema of any

@@ -25,6 +25,7 @@
  *   fpnmt_sample_step, fpnmt_sample_uniform    sampled decoding (temperature, top-k, top-p)    not in the reference
  *   fpnmt_logits_constrain                     n-gram blocking, repetition penalty, min length  not in the reference
  *   fpnmt_ciderd_reward, fpnmt_scst_pack       CIDEr-D reward and advantages on the device     not in the reference
+ *   fpnmt_ciderd_consensus                     consensus (MBR) caption selection under CIDEr-D not in the reference
  *   fpnmt_logits_ensemble                      several models' logits rows folded into one     not in the reference
  *   fpnmt_xent_distill_fwd_bwd                 smoothed CE mixed with KL to teachers' rows     not in the reference
  *
@@ -1248,6 +1249,42 @@ int fpnmt_scst_pack(int b, int n, int mode, const double* reward, const double* 
                     const int32_t* hist, int hist_ld, const int32_t* slen, const int32_t* fin, const float* score,
                     int start_token, int end_token, int max_tokens, long long* tok, int width, float* adv,
                     double* scalars, fpnmt_stream_t stream);
+
+/* Consensus (minimum-Bayes-risk) caption selection under CIDEr-D (not in the
+ * reference; csrc/consensus.hip): among the n candidates of an image, rows
+ * img * n .. img * n + n - 1 of the sampler's or the beam search's device
+ * state (candidate r = hist[r][1 : 1 + len[r] - fin[r]], clamped to
+ * min(hist_ld - 1, max_len) tokens), the one that agrees most with the others.
+ *   sim(h, r)  CiderDReward's score_one of h with r as the ONLY reference:
+ *              tf * idf vectors with the corpus's idf, counts clipped as
+ *              min(w_h, w_r) * w_r, each order divided by nh * nr where both
+ *              are non-zero and multiplied by gauss[|len_h - len_r|] (lengths
+ *              are bigram counts), the mean of the four orders, x 10. Not
+ *              symmetric.
+ *   util[r]    (fp64, rows = images * n) = sum over j != s of p_j sim(c_s,
+ *              c_j) / sum over j != s of p_j for r = img * n + s, both sums
+ *              over ascending j, 0 where the denominator is 0; p = weight
+ *              (non-negative, per row) or 1 where weight is NULL. Self is
+ *              excluded by index: a duplicate at another index counts. An
+ *              empty caption has utility 0 and contributes 0; n = 1 gives 0.
+ *   pick[img]  the index s < n of the greatest util, ties to the lowest.
+ *   pair       NULL, or [images][n][n] fp64: pair[img][s][j] = sim(c_s, c_j),
+ *              the diagonal included.
+ * Of the tables only df_keys, df_idf, n_df, idf_absent, gauss, n_gauss and
+ * max_len are read. One block per image keeps every candidate's keys and
+ * weights in LDS: 16 n E + 64 E + 44 n bytes with E = L + (L - 1) + (L - 2) +
+ * (L - 3) (the terms above zero) at L = min(hist_ld - 1, max_len) must not
+ * exceed 160 KiB (n = 64 up to L = 38, n = 16 up to L = 128), else
+ * FPNMT_E_UNSUPPORTED, as for n > FPNMT_CONSENSUS_MAX_CANDS, hist_ld - 1 >
+ * max_len and max_len > FPNMT_CIDER_MAX_LEN. images == 0 returns 0 without a
+ * launch. fp64, fixed-order sums, no atomics: bitwise repeatable, and an
+ * image's outputs do not depend on the other images of the launch. No
+ * allocation, no synchronisation, capturable.                              */
+#define FPNMT_CONSENSUS_MAX_CANDS 64
+int fpnmt_ciderd_consensus(const fpnmt_cider_tables* t, int images, int n, const int32_t* hist, int hist_ld,
+                           const int32_t* len, const int32_t* fin, const double* weight /* rows, or NULL: uniform */,
+                           double* util /* rows */, int32_t* pick /* images */,
+                           double* pair /* images * n * n, or NULL */, fpnmt_stream_t stream);
 
 /* ---- MobileNetV2 backbone (models/mobilenet.py:43-72 ->
  * keras MobileNetV2(alpha=1.0), models/retinanet.py:274) -------------------
