@@ -1645,11 +1645,20 @@ int fpnmt_maxpool2d_bwd_act(int dtype, int n, int h, int w, int c, int kh, int k
   return check_launch("maxpool_bwd_act");
 }
 
+// fpn_*_kernel load and store 16-byte vectors unconditionally
+static bool fpn_aligned(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if ((uintptr_t)p % 16) return false;
+  return true;
+}
+
 int fpnmt_fpn_topdown_fwd(int dtype, int n, int c, int h5, int w5, int h4, int w4, int h3, int w3,
                           const void* lat5, const void* lat4, const void* lat3, void* p4m, void* p3m,
                           fpnmt_stream_t stream) {
   const int vn = dtype == FPNMT_BF16 ? 8 : 4;
   if (c % vn) return fail(FPNMT_E_UNSUPPORTED, "fpn_topdown: channels must be a multiple of 8 (bf16) / 4 (f32)");
+  if (!fpn_aligned({lat5, lat4, lat3, p4m, p3m}))
+    return fail(FPNMT_E_ARG, "fpn_topdown_fwd: every pointer must be 16-byte aligned");
   const long long total = (long long)n * (h3 * w3 + h4 * w4) * (c / vn);
   if (total <= 0) return 0;
   const int g = grid_for(total, 256);
@@ -1668,6 +1677,8 @@ int fpnmt_fpn_topdown_bwd(int dtype, int n, int c, int h5, int w5, int h4, int w
                           int accumulate_lat5, fpnmt_stream_t stream) {
   const int vn = dtype == FPNMT_BF16 ? 8 : 4;
   if (c % vn) return fail(FPNMT_E_UNSUPPORTED, "fpn_topdown: channels must be a multiple of 8 (bf16) / 4 (f32)");
+  if (!fpn_aligned({d_p4m, d_p3m, d_lat4, d_lat5}))
+    return fail(FPNMT_E_ARG, "fpn_topdown_bwd: every pointer must be 16-byte aligned");
   const long long total = (long long)n * (h4 * w4 + h5 * w5) * (c / vn);
   if (total <= 0) return 0;
   const int g = grid_for(total, 256);

@@ -430,7 +430,11 @@ int fpnmt_maxpool2d_bwd_act(int dtype, int n, int h, int w, int c, int kh, int k
  * P4m = lat4 + up(lat5 -> h4 x w4);  P3m = lat3 + up(P4m -> h3 x w3)
  * up = TF2 nearest resize (half-pixel centres): src = min(floor((d+.5)*in/out), in-1)
  * All (n, h_i, w_i, c). bwd: d_lat5 (+)= down(d_P4 + down(d_P3)),
- * d_lat4 = d_P4m + down(d_P3m); d_lat3 = d_P3m (caller aliases, no copy). */
+ * d_lat4 = d_P4m + down(d_P3m); d_lat3 = d_P3m (caller aliases, no copy).
+ * h3 = w3 = 0 with null lat3 / p3m / d_p3m is the plain upsample-and-add.
+ * c must be a multiple of 8 (bf16) / 4 (f32) and every non-null pointer
+ * 16-byte aligned (the kernels move 16-byte vectors): FPNMT_E_UNSUPPORTED /
+ * FPNMT_E_ARG otherwise, before any launch.                                */
 int fpnmt_fpn_topdown_fwd(int dtype, int n, int c, int h5, int w5, int h4, int w4, int h3,
                           int w3, const void* lat5, const void* lat4, const void* lat3,
                           void* p4m, void* p3m, fpnmt_stream_t stream);
