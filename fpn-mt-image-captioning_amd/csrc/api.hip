@@ -40,6 +40,16 @@ void log_attn(const char* op, const char* kernel, int dtype, int b, int h, int l
     std::fflush(f);
   }
 }
+void log_conv(const char* op, const char* kernel, int dtype, int n, int h, int w, int c, int k, int r, int s, int grid,
+              int levels, long long pixels) {
+  if (FILE* f = gemm_log()) {
+    std::fprintf(f, "conv op=%s kernel=%s dtype=%s n=%d h=%d w=%d c=%d k=%d r=%d s=%d grid=%d", op, kernel,
+                 dtype == FPNMT_BF16 ? "bf16" : "f32", n, h, w, c, k, r, s, grid);
+    if (levels >= 0) std::fprintf(f, " levels=%d pixels=%lld", levels, pixels);
+    std::fputc('\n', f);
+    std::fflush(f);
+  }
+}
 
 __global__ void zero2d_kernel(char* __restrict__ p, size_t pitch, size_t width, size_t rows) {
   // 16-B stores where the row start and width allow it, bytes otherwise

@@ -19,9 +19,18 @@ int fail(int code, const std::string& msg);
 int check_launch(const char* what);
 // FPNMT_GEMM_LOG=<file> (api.hip): the launch log, opened once per process;
 // null when the variable is unset. One line per GEMM launch (log_gemm,
-// gemm_dispatch.h) and one per attention launcher:
+// gemm_dispatch.h), one per attention launcher:
 //   attn op=<fwd|bwd|views_fwd|views_bwd|decode> kernel=<name> dtype=<f32|bf16> b= h= lq= lk= d= [n=<views>]
+// and one per launch of a convolution kernel outside the GEMM dispatch (the
+// stem and single-filter hooks of conv_stem.hip / conv_n1.hip; written only
+// when the hook launched, nothing when it declines and the implicit GEMM runs):
+//   conv op=<fwd|bwd_data|bwd_filter> kernel=<stem7x7s2|stem_wgrad112|stem_wgrad256|n1_fwd|n1_bwd_data|n1_bwd_filter>
+//        dtype=<f32|bf16> n= h= w= c= k= r= s= grid=<blocks in x> [levels=<live levels> pixels=<their pixel total>]
+// n, h, w are the input shape (grouped single-filter launches: the first live
+// level's, with levels= and pixels= appended).
 FILE* gemm_log();
+void log_conv(const char* op, const char* kernel, int dtype, int n, int h, int w, int c, int k, int r, int s, int grid,
+              int levels = -1, long long pixels = -1);
 void log_attn(const char* op, const char* kernel, int dtype, int b, int h, int lq, int lk, int d, int n_views = -1);
 inline void log_attn(const char* op, const char* kernel, const fpnmt_attn_desc* d, int n_views = -1) {
   log_attn(op, kernel, d->dtype, d->b, d->h, d->lq, d->lk, d->d, n_views);

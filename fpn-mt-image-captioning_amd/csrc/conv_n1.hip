@@ -325,14 +325,14 @@ bool n1_aligned(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 template <typename T>
 int n1_fwd_t(const N1Args& a, const void* w, const float* scale, const float* bias, int act, float alpha,
-             hipStream_t s) {
+             hipStream_t s, int& grid) {
   constexpr int VN = N1V<T>::n;
   const int cv = a.C / VN;
   const long long P = a.P;
   const int LPP = cv >= 64 ? 64 : cv;
   const long long waves = (P * LPP + 63) / 64;
   // ~4 waves per SIMD over the chip, each looping over ~4 rounds
-  const int grid = (int)std::min<long long>(1024, std::max<long long>(1, (waves + 7) / 8));
+  grid = (int)std::min<long long>(1024, std::max<long long>(1, (waves + 7) / 8));
   const T* wt = (const T*)w;
   const T* zp = (const T*)zero16_ptr();
   switch (cv) {
@@ -346,27 +346,28 @@ int n1_fwd_t(const N1Args& a, const void* w, const float* scale, const float* bi
 }
 
 template <typename T>
-int n1_bwd_data_t(const N1Args& a, const void* w, int act_in, hipStream_t s) {
+int n1_bwd_data_t(const N1Args& a, const void* w, int act_in, hipStream_t s, int& grid) {
   constexpr int VN = N1V<T>::n;
   const int cv = a.C / VN;
   const long long total = (long long)a.P * cv;
   // grid * 256 a multiple of cv (a power of two <= 128): every thread keeps one
   // chunk; 2 pixels per thread (the LDS weight staging per block vs the
   // serial rounds' memory latency)
-  const int grid = (int)std::min<long long>(8192, std::max<long long>(1, (total + 511) / 512));
+  grid = (int)std::min<long long>(8192, std::max<long long>(1, (total + 511) / 512));
   hipLaunchKernelGGL((n1_bwd_data_kernel<T>), dim3(grid), dim3(256), 0, s, a, (const T*)w, act_in,
                      (const T*)zero16_ptr());
   return check_launch("n1_bwd_data_kernel");
 }
 
 template <typename T>
-int n1_bwd_filter_t(const N1Args& a, float* dw, hipStream_t s) {
+int n1_bwd_filter_t(const N1Args& a, float* dw, hipStream_t s, int& grid) {
   const long long P = a.P;
   if (P <= 0) return 0;
   const int cols = a.R * a.S * a.C;
   long long nb = std::min<long long>(1024, std::max<long long>(1, P / 16));
   const long long ppb = (P + nb - 1) / nb;
   nb = (P + ppb - 1) / ppb;
+  grid = (int)nb;
   float* part = partial_f32(nb * cols);
   if (!part) return fail(FPNMT_E_ARG, "conv2d_bwd_filter (k = 1): needs the process workspace (fpnmt_set_workspace)");
   hipLaunchKernelGGL((n1_bwd_filter_kernel<T>), dim3((unsigned)nb), dim3(256), 0, s, a, part, (int)ppb,
@@ -424,17 +425,26 @@ int conv_n1(int pass, const fpnmt_conv_desc* d, int n_levels, const fpnmt_conv_l
   N1Args a;
   if (n1_args(d, n_levels, lv, pass, act_in, a)) return 0;
   if (a.nl == 0) return 0;  // nothing to compute: the generic path handles empty outputs
-  int st = 0;
+  int st = 0, grid = 0;
   if (pass == 0) {  // fwd: lv.x input, lv.y output
     if (!n1_ptrs_aligned(a, true, false, false)) return 0;
-    st = bf ? n1_fwd_t<bf16>(a, w, scale, bias, d->act, d->act_alpha, s)
-            : n1_fwd_t<float>(a, w, scale, bias, d->act, d->act_alpha, s);
+    st = bf ? n1_fwd_t<bf16>(a, w, scale, bias, d->act, d->act_alpha, s, grid)
+            : n1_fwd_t<float>(a, w, scale, bias, d->act, d->act_alpha, s, grid);
   } else if (pass == 1) {  // bwd-data: lv.x dz, lv.y dx, lv.dz = y_in (mask) or null
     if (!n1_ptrs_aligned(a, false, true, true)) return 0;
-    st = bf ? n1_bwd_data_t<bf16>(a, w, act_in, s) : n1_bwd_data_t<float>(a, w, act_in, s);
+    st = bf ? n1_bwd_data_t<bf16>(a, w, act_in, s, grid) : n1_bwd_data_t<float>(a, w, act_in, s, grid);
   } else {  // bwd-filter: lv.x input, lv.dz output gradient
     if (scale || !n1_ptrs_aligned(a, true, false, false)) return 0;
-    st = bf ? n1_bwd_filter_t<bf16>(a, dw, s) : n1_bwd_filter_t<float>(a, dw, s);
+    st = bf ? n1_bwd_filter_t<bf16>(a, dw, s, grid) : n1_bwd_filter_t<float>(a, dw, s, grid);
+  }
+  if (!st) {
+    static const char* const op[3] = {"fwd", "bwd_data", "bwd_filter"};
+    static const char* const kernel[3] = {"n1_fwd", "n1_bwd_data", "n1_bwd_filter"};
+    int first = 0;  // the first live level (n1_args skips the empty ones the same way)
+    while (first < n_levels - 1 && a.x[0] != lv[first].x) ++first;
+    const bool grouped = n_levels > 1;
+    log_conv(op[pass], kernel[pass], d->dtype, lv[first].n, lv[first].h, lv[first].w, d->c, 1, d->r, d->s, grid,
+             grouped ? a.nl : -1, grouped ? (long long)a.P : -1);
   }
   return st ? st : 1;
 }

@@ -448,6 +448,7 @@ int stem_conv_bwd_filter(const fpnmt_conv_desc* d, const void* x, const void* dz
     hipLaunchKernelGGL(stem_wgrad_kernel<256>, dim3(grid), dim3(SW_THREADS), 0, s, a);
   int st = check_launch("stem_wgrad_kernel");
   if (!st) st = wgrad_slabs_reduce(dw_hwio, SW_M, 64, 64, grid, col_scale, slab, s);
+  if (!st) log_conv("bwd_filter", WP <= 112 ? "stem_wgrad112" : "stem_wgrad256", d->dtype, d->n, d->h, d->w, 3, 64, 7, 7, grid);
   return st ? st : 1;
 }
 
@@ -486,6 +487,7 @@ int stem_conv_fwd(const fpnmt_conv_desc* d, const void* x, const void* w_ohwi, c
   else
     hipLaunchKernelGGL(stem7x7s2_kernel<FPNMT_ACT_NONE>, g, dim3(256), 0, s, a);
   const int st = check_launch("stem7x7s2_kernel");
+  if (!st) log_conv("fwd", "stem7x7s2", d->dtype, d->n, d->h, d->w, 3, d->k, 7, 7, grid);
   return st ? st : 1;
 }
 

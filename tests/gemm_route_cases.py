@@ -604,7 +604,8 @@ def plants(case, inp, lin):
 
 # ------------------------------------------------------------------ routing
 def parse_log(lines):
-    return [dict(kv.split("=") for kv in ln.split()[1:]) for ln in lines if ln.strip()]
+    """The GEMM launch lines (first word: the dtype); `conv` / `attn` lines are other launchers'."""
+    return [dict(kv.split("=") for kv in ln.split()[1:]) for ln in lines if ln.strip() and ln.split()[0] in ("bf16", "f32")]
 
 
 def route_errors(case, lines):

@@ -27,6 +27,9 @@ def _port():
 
 
 def _run(rank, world, port, fn, outdir):
+    # forked child: keep off the parent's OpenMP pool (its worker threads do not
+    # exist here; a parallel region entered after tests that spun the pool up hangs)
+    torch.set_num_threads(1)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world, init_method=f"tcp://127.0.0.1:{port}")
     try:

@@ -207,7 +207,8 @@ def _scenario(child, key):
 
 
 def _recs(lines):
-    return [dict(kv.split("=") for kv in ln.split()[1:]) for ln in lines if ln.strip()]
+    # GEMM launch lines only (first word: the dtype); a `conv` line is the stem / single-filter kernels' own
+    return [dict(kv.split("=") for kv in ln.split()[1:]) for ln in lines if ln.strip() and ln.split()[0] in ("bf16", "f32")]
 
 
 def _assert_equal(a, b, what):

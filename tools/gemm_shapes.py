@@ -19,9 +19,10 @@ CFG = {0: "128x128x64", 1: "64x64x32", 2: "64x64x64", 3: "128x128x32", 4: "32x32
        110: "pipeWG128", 130: "pipe128x64e0", 131: "pipe64x64", 132: "pipe64x64s2", 133: "pipe128x256s2",
        134: "pipe64x64s4", 150: "wgjobs"}
 
-# the attention launchers' route lines (first word `attn`) are no GEMM launches
+# the attention launchers' route lines (first word `attn`) and the stem /
+# single-filter conv kernels' (first word `conv`) are no GEMM launches
 log = [dict(kv.split("=") for kv in ln.split()[1:]) for ln in open(sys.argv[1])
-       if ln.strip() and ln.split()[0] != "attn"]
+       if ln.strip() and ln.split()[0] not in ("attn", "conv")]
 # deferred weight-gradient GEMMs (cfg 150) are queued, not launched: they run
 # at the flush as grouped gemm_wg_jobs_kernel launches, reported separately
 # (likewise the queued conv weight gradients, cfg 111, run by the grouped
